@@ -12,6 +12,13 @@ Multi-GPU: one process per GPU, envs sharded by global env id (env_offset = rank
 no collective in the step -> weak scaling; the timed region is bracketed by barrier +
 synchronize and the max over ranks is reported.
 
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and
+prints the result line; its rooflines are derived from those same N launches and a committed profile,
+not from runs of their own. `--full` adds the CPU baselines (cpu_baseline below), which take
+--cpu-budget seconds of host time after the timed region. `--dump-outputs DIR` writes what the last
+timed step returned (the State a caller of `env.step` receives: obs, reward, done, data, metrics, info)
+as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
+
 Extra JSON objects:
   roofline        the step kernel against HBM: algorithmic bytes per env-step
                   x envs per launch / average launch time from HIP events on the launch stream.
@@ -24,6 +31,7 @@ Extra JSON objects:
   cpu_baseline    the fp64 C oracle (oracle/, a restatement of the same step) over OpenMP on the
                   host cores this job may use (affinity, capped by the cgroup CPU quota), on a
                   bounded sample (rank 0, N=1 only), plus BASELINE configs[0] (C1): 1 env, 1 core.
+                  Only with --full (null otherwise).
 
 --strong keeps 4096 envs in total over the N ranks (strong scaling) instead of 4096 per rank.
 
@@ -220,6 +228,36 @@ def cpu_baseline(task: str, use_imitation: bool, budget_s: float, threads: int):
                       f"OpenMP {threads} threads"}
 
 
+DUMP_BYTES = 64 * 10**6  # --dump-outputs: upper bound on what all ranks write together
+
+
+def dump_outputs(path: str, state, n: int, rank: int, world: int) -> None:
+    """Write the State the last timed step returned as <path>/<name>.npy (rank r > 0: <name>.rank<r>.npy):
+    float fields as float32, integer fields (step counters, RNG words) as float64, which holds them
+    exactly. Above DUMP_BYTES in all, every array keeps the same seeded sample of env rows (env_rows.npy)."""
+    fields = {"obs_state": state.obs["state"], "obs_privileged_state": state.obs["privileged_state"],
+              "reward": state.reward, "done": state.done, "qpos": state.data.qpos, "qvel": state.data.qvel,
+              "qacc_warmstart": state.data.qacc_warmstart, "ctrl": state.data.ctrl}
+    fields.update({f"metrics_{k.replace('/', '_')}": v for k, v in state.metrics.items()})
+    fields.update({f"info_{k}": v for k, v in state.info.items()})
+    arrays = {}
+    for name, t in fields.items():
+        if t.numel() == 0:  # a field this configuration does not carry (the reference motion without imitation)
+            continue
+        a = t.detach().cpu().numpy()
+        assert a.shape[0] == n, (name, a.shape)
+        arrays[name] = a.astype(np.float32 if a.dtype.kind == "f" else np.float64)
+    per_env = sum(a.nbytes // n for a in arrays.values()) + 8
+    headers = 128 * (len(arrays) + 1)  # an .npy file of these shapes starts with a 128-byte header
+    keep = min(n, max(0, DUMP_BYTES // world - headers) // per_env)
+    rows = np.arange(n) if keep == n else np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+    arrays = {name: a[rows] for name, a in arrays.items()}
+    arrays["env_rows"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -228,7 +266,12 @@ def main():
     ap.add_argument("--config", default="C2", choices=sorted(CONFIGS),
                     help="BASELINE.json workload: C2 flat (the metric), C3 +imitation, C4 rough+DR, C5 rough+DR+backlash")
     ap.add_argument("--envs", type=int, default=0, help="envs per GPU (0 = the config's)")
-    ap.add_argument("--cpu-budget", type=float, default=15.0, help="seconds of CPU-baseline sampling (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baselines (cpu_baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the State the last timed step returned as DIR/<name>.npy (at most 64 MB)")
+    ap.add_argument("--cpu-budget", type=float, default=15.0,
+                    help="with --full: seconds of CPU-baseline sampling (0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = every host core this job may use")
     ap.add_argument("--strong", action="store_true", help="4096 envs in total over the ranks (strong scaling)")
     ap.add_argument("--step-mode", default="auto", choices=["auto", "throughput", "latency", "paired", "latency_x2"],
@@ -307,8 +350,11 @@ def main():
                   ev_all[0].elapsed_time(ev_all[1]) / K)
     ok = bool(torch.isfinite(state.obs["state"]).all().item())
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, state, n, rank, world)
+
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_budget > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_budget > 0:
         thr = args.cpu_threads or host_cores()
         cpu = cpu_baseline(cfg["task"], cfg["imitation"], args.cpu_budget, thr)
         cpu["host_cores"] = host_cores()

@@ -75,22 +75,8 @@ def test_fingerprint_sees_every_baked_edit():
     assert model_fingerprint(m) == model_fingerprint(m2)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="needs the reference XMLs (build container)")
-def test_edited_scenes_are_reproducible_from_the_xml():
-    """The committed test scenes are exactly what the model compiler makes of the edited reference
-    XML (tools/build_assets.py EDITED), and the shipped flat scene of the unedited XML."""
-    import sys
-    import tempfile
-    sys.path.insert(0, os.path.join(os.path.dirname(MODELS), "..", "..", "tools"))
-    import build_assets as B
-    from open_duck_playground_amd.mjcf import compile_mjcf
-    for name, (re_, se) in B.EDITED.items():
-        with tempfile.TemporaryDirectory() as td:
-            m = compile_mjcf(B.edited_scene(td, re_, se), timestep=0.002)
-        assert model_fingerprint(m) == model_fingerprint(Model.load(os.path.join(MODELS, f"{name}.npz"))), name
-    with tempfile.TemporaryDirectory() as td:
-        m = compile_mjcf(B.edited_scene(td, [], []), timestep=0.002)
-    assert model_fingerprint(m) == model_fingerprint(Model.load(constants.task_to_xml("flat_terrain")))
+# (that the committed scenes are what the model compiler makes of the reference's XML needs the
+# reference's own files, which are not part of this repository: tools/build_assets.py --check)
 
 
 def _header_tables(variant):

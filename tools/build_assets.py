@@ -105,7 +105,23 @@ def build_edited(out_dir: str):
         print(name, m.nq, m.nv, m.nu, list(m.opt_gravity))
 
 
+def check_edited(models_dir: str) -> None:
+    """--check: the committed test scenes are exactly what the model compiler makes of the edited
+    reference XML (EDITED), and the shipped flat scene of the unedited XML. Writes nothing."""
+    from open_duck_playground_amd.cabi import model_fingerprint
+    from open_duck_playground_amd.mjcf import Model
+    for name, (re_, se) in list(EDITED.items()) + [("flat_terrain", ([], []))]:
+        with tempfile.TemporaryDirectory() as td:
+            m = compile_mjcf(edited_scene(td, re_, se), timestep=0.002)
+        path = os.path.join(OUT, "flat_terrain.npz") if name == "flat_terrain" else os.path.join(models_dir, f"{name}.npz")
+        if model_fingerprint(m) != model_fingerprint(Model.load(path)):
+            raise SystemExit(f"{path} is not what the model compiler makes of the reference XML ({name})")
+        print("reproduced", name)
+
+
 def main():
+    if "--check" in sys.argv[1:]:
+        return check_edited(os.path.join(os.path.dirname(__file__), "..", "tests", "golden", "models"))
     os.makedirs(OUT, exist_ok=True)
     models = {}
     for task, fname in TASKS.items():
