@@ -2,7 +2,7 @@
 //
 // One launch per env-step runs the whole of Joystick.step (joystick.py:323-481):
 // imitation phase + reference motion, action delay, push, motor-target rate limit, 10
-// fused physics substeps (duck_team.h: 16 lanes per env; duck_physics.h: one lane per env),
+// fused physics substeps (duck_team.h: 16 lanes per env; duck_physics.h: the LDS layout),
 // contacts, obs, termination, rewards, info bookkeeping, and (optionally) the training
 // wrappers EpisodeWrapper + BraxAutoResetWrapper. Per-env state never leaves LDS between
 // substeps; HBM sees one read and one write of the state per env-step.
@@ -46,29 +46,28 @@ struct KArgs {
   unsigned* err;  // the handle's sticky device error word (host-mapped; duck_device_error)
 };
 
-// Launch geometry: 16 lanes per env (a team), 16 envs (4 waves) per workgroup, so 4096 envs are
-// exactly one workgroup per CU.
-constexpr int WG = 16;
-constexpr int EPW = 4;
-constexpr int TPB = WG * TEAM;
-static_assert(TPB == TPB_TEAM, "load_model_tables assumes the kernels' block size");
-constexpr int SW = 1;  // slice stride (contiguous per-env slices)
+// Launch geometry (duck_team.h): 16 lanes per env (TEAM), 16 envs = 4 waves per workgroup (TEAM_WG,
+// TPB threads), so 4096 envs are exactly one workgroup per CU.
 
-// this lane's env within the workgroup (-1: idle lane) and its rank in the env's team
+// this lane's env within the workgroup and its rank in the env's team
 DK int local_env(int& lane) {
   lane = threadIdx.x % TEAM;
   return threadIdx.x / TEAM;
 }
 
+// env t's slice of the workgroup's LDS (contiguous: element k at L[k])
 template <class Md, int LAT = 0>
-DK Slice<SW> env_slice(float* lds, int t) {
-  return Slice<SW>{(lds_float*)(lds + t * TLay<Md, LAT>::STRIDE)};
+DK lds_float* env_slice(float* lds, int t) {
+  return (lds_float*)(lds + t * TLay<Md, LAT>::STRIDE);
 }
 
+// one substep (TPhys::step). The forwarding layer is kept: with step called directly the height-field
+// scenes' step_kernel and phys_step_dni compile to different instructions (same count, other address
+// arithmetic in the contact stores)
 template <class Md>
-DK void phys_step(Slice<SW> L, int lane, bool integrate, bool want_out, float* aux, int aux_stride, float* scratch,
+DK void phys_step(lds_float* L, int lane, bool integrate, bool want_out, float* aux, int aux_stride, float* scratch,
                   int sstride, const float* hfield) {
-  TPhys<Md>::step(L.p, lane, integrate, want_out, aux, aux_stride, scratch, sstride, hfield);
+  TPhys<Md>::step(L, lane, integrate, want_out, aux, aux_stride, scratch, sstride, hfield);
 }
 
 // the physics_kernel (mjx_env.step / mjx.forward parity entry) runs its substeps through one
@@ -77,12 +76,11 @@ DK void phys_step(Slice<SW> L, int lane, bool integrate, bool want_out, float* a
 // needed 512 VGPRs + 86 spilled, the pressure under which the allocator misplaced split copies
 // ahead of an exec restore)
 template <class Md>
-__device__ __noinline__ void phys_step_dni(Slice<SW> L, int lane, bool integrate, bool want_out, float* aux,
+__device__ __noinline__ void phys_step_dni(lds_float* L, int lane, bool integrate, bool want_out, float* aux,
                                            int aux_stride, float* scratch, int sstride, const float* hfield) {
   phys_step<Md>(L, lane, integrate, want_out, aux, aux_stride, scratch, sstride, hfield);
 }
 
-template <int WG>
 struct Col {  // SoA accessor for env e
   float* p;
   int n;
@@ -143,10 +141,10 @@ DK void sample_command(const duck_env_config& c, const RT& r, int slot, float* c
 }
 
 // per-env model values: nominal (constexpr) or this env's domain-randomised record
-template <class Md, int WG>
-DK void load_dyn(const KArgs& A, int e, Slice<WG> L) {
+template <class Md>
+DK void load_dyn(const KArgs& A, int e, lds_float* L) {
   using Ly = Lay<Md>;
-  Phys<Md, WG>::set_nominal(L);
+  Phys<Md>::set_nominal(L);
   if (A.dr) {
     const duck_dr_layout& D = A.drl;
     const int n = A.n;
@@ -166,7 +164,7 @@ DK void load_dyn(const KArgs& A, int e, Slice<WG> L) {
 
 // load_dyn with the team's lanes: nominal block from the LDS model blob, then the env's DR record
 template <class Md, int LAT = 0>
-DK void load_dyn_team(const KArgs& A, int e, Slice<SW> L, int lane) {
+DK void load_dyn_team(const KArgs& A, int e, lds_float* L, int lane) {
   using Ly = Lay<Md>;
   using TP = TPhys<Md, LAT>;
   constexpr int NDYN = Md::NB + 3 + 2 * Md::NV + Md::NQ + Md::NU;
@@ -188,127 +186,28 @@ DK void load_dyn_team(const KArgs& A, int e, Slice<SW> L, int lane) {
   }
 }
 
-// Joystick._get_obs (joystick.py:487-620) / Standing._get_obs (standing.py:462-575); reads the
-// last forward's outputs from the slice
-// Observation sinks: GObs writes obs/priv rows in HBM directly; SObs stages the privileged row
-// (whose prefix is the state row) in the env slice's dead H/row storage, from where the team
-// stores both rows with coalesced 16-lane stores (step_kernel)
-struct GObs {
-  float* obs;
-  float* priv;
-  int obs_size;
-  DK void operator()(int k, float v) const {
-    if (k < obs_size) obs[k] = v;
-    priv[k] = v;
-  }
-};
-template <int WG>
+// Observation sink: the privileged row (whose prefix is the state row) is staged in the env slice's
+// H/row storage, dead after the last forward, from where the team stores both rows with coalesced
+// 16-lane stores (the end of step_env and of reset_kernel)
 struct SObs {
-  Slice<WG> L;
-  int base;
-  DK void operator()(int k, float v) const { L[base + k] = v; }
+  lds_float* row;
+  DK void operator()(int k, float v) const { row[k] = v; }
 };
 
-template <class Md, int WG, class FA, class OS, class RT>
-DK void write_obs(const KArgs& A, int e, Slice<WG> L, const FA& F, const OS& out, const RT& r, int slot_base,
-                  int imitation_i) {
-  using Ly = Lay<Md>;
-  const duck_env_config& c = A.cfg;
-  const duck_layout& Lo = A.lay;
-  constexpr int NU = Md::NU;
-  float gyro[3], acc[3], grav[3];
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    gyro[k] = L[Ly::SENS + c.sens_gyro + k];
-    acc[k] = L[Ly::SENS + c.sens_accelerometer + k];
-    grav[k] = -L[Ly::IMUR + k];
-  }
-  float ngrav[3];
-#pragma unroll
-  for (int k = 0; k < 3; k++)
-    ngrav[k] = grav[k] + (2.0f * r.u(slot_base + SLOT_GRAVITY + k) - 1.0f) * c.noise_level * c.noise_gravity;
-  // IMU delay history (joystick.py:521-530); the delayed sample is never emitted
-#pragma unroll
-  for (int k = 8; k >= 3; k--) F[Lo.imu_history + k] = F[Lo.imu_history + k - 3];
-#pragma unroll
-  for (int k = 0; k < 3; k++) F[Lo.imu_history + k] = ngrav[k];
-  int o = 0;
-  auto put = [&](float v) { out(o++, v); };
-#pragma unroll
-  for (int k = 0; k < 3; k++) put(gyro[k] + (2.0f * r.u(slot_base + SLOT_GYRO + k) - 1.0f) * c.noise_level * c.noise_gyro);
-#pragma unroll
-  for (int k = 0; k < 3; k++)
-    put(acc[k] + (2.0f * r.u(slot_base + SLOT_ACCEL + k) - 1.0f) * c.noise_level * c.noise_accelerometer);
-#pragma unroll
-  for (int k = 0; k < 7; k++) put(F[Lo.command + k]);
-  for (int a = 0; a < NU; a++) {
-    float ja = L[Ly::QPOS + c.actuator_qposadr[a]];
-    if (c.backlash_qposadr[a] >= 0) ja += L[Ly::QPOS + c.backlash_qposadr[a]];
-    put(ja + (2.0f * r.u(slot_base + SLOT_QPOS + a) - 1.0f) * c.noise_level * c.qpos_noise_scale[a] - c.default_actuator[a]);
-  }
-  for (int a = 0; a < NU; a++) {
-    const float jv = L[Ly::QVEL + c.actuator_qveladr[a]];
-    put((jv + (2.0f * r.u(slot_base + SLOT_QVEL + a) - 1.0f) * c.noise_level * c.noise_joint_vel) * c.dof_vel_scale);
-  }
-  for (int a = 0; a < NU; a++) put(F[Lo.last_act + a]);
-  for (int a = 0; a < NU; a++) put(F[Lo.last_last_act + a]);
-  for (int a = 0; a < NU; a++) put(F[Lo.last_last_last_act + a]);
-  const bool joystick = Lo.task == DUCK_TASK_JOYSTICK;
-  if (joystick)
-    for (int a = 0; a < NU; a++) put(F[Lo.motor_targets + a]);
-  put(L[Ly::OCON]);
-  put(L[Ly::OCON + 1]);
-  if (joystick) {
-    put(F[Lo.imitation_phase]);
-    put(F[Lo.imitation_phase + 1]);
-  }
-  int p = o;
-  auto pp = [&](float v) { out(p++, v); };
-#pragma unroll
-  for (int k = 0; k < 3; k++) pp(gyro[k]);
-#pragma unroll
-  for (int k = 0; k < 3; k++) pp(acc[k]);
-#pragma unroll
-  for (int k = 0; k < 3; k++) pp(grav[k]);
-#pragma unroll
-  for (int k = 0; k < 3; k++) pp(L[Ly::SENS + c.sens_local_linvel + k]);
-#pragma unroll
-  for (int k = 0; k < 3; k++) pp(L[Ly::SENS + c.sens_global_angvel + k]);
-  for (int a = 0; a < NU; a++) {
-    float ja = L[Ly::QPOS + c.actuator_qposadr[a]];
-    if (c.backlash_qposadr[a] >= 0) ja += L[Ly::QPOS + c.backlash_qposadr[a]];
-    pp(ja - c.default_actuator[a]);
-  }
-  for (int a = 0; a < NU; a++) pp(L[Ly::QVEL + c.actuator_qveladr[a]]);
-  pp(L[Ly::QPOS + 2]);
-  for (int a = 0; a < NU; a++) pp(L[Ly::AF + a]);
-  pp(L[Ly::OCON]);
-  pp(L[Ly::OCON + 1]);
-#pragma unroll
-  for (int k = 0; k < 3; k++) pp(L[Ly::SENS + c.sens_left_foot_linvel + k]);
-#pragma unroll
-  for (int k = 0; k < 3; k++) pp(L[Ly::SENS + c.sens_right_foot_linvel + k]);
-  pp(F[Lo.feet_air_time]);
-  pp(F[Lo.feet_air_time + 1]);
-  if (Lo.imitation)
-    for (int k = 0; k < 40; k++) pp(F[Lo.ref_motion + k]);
-  if (joystick) {
-    pp((float)imitation_i);
-    pp(F[Lo.imitation_phase]);
-    pp(F[Lo.imitation_phase + 1]);
-  }
-}
-
-// write_obs with the team's lanes splitting the rows (step_kernel): lane a < NU takes actuator
-// a's entries, lanes 0-2 the 3-vectors, lanes 0-1 the pairs; same values at the same offsets
+// Joystick._get_obs (joystick.py:487-620) / Standing._get_obs (standing.py:462-575); reads the
+// last forward's outputs from the slice. The team's lanes split the rows: lane a < NU takes
+// actuator a's entries, lanes 0-2 the 3-vectors, lanes 0-1 the pairs. The noise draws are slots
+// slot_base + SLOT_* of r (step: 0, reset: RSLOT_OBS). A lane reads from F only what it wrote itself
+// or what was there before the kernel: whatever crosses lanes goes through `out` and a TSYNC
 template <class Md, class FA, class OS, class RT>
-DK void write_obs_team(const KArgs& A, int lane, Slice<SW> L, const FA& F, const OS& out, const RT& r,
-                       int imitation_i) {
+DK void write_obs_team(const KArgs& A, int lane, lds_float* L, const FA& F, const OS& out, const RT& r,
+                       int slot_base, int imitation_i) {
   using Ly = Lay<Md>;
   const duck_env_config& c = A.cfg;
   const duck_layout& Lo = A.lay;
   constexpr int NU = Md::NU;
   static_assert(NU <= TEAM, "an actuator per lane");
+  static_assert(priv_row_max(NU) <= Ly::HSZ + 4 * Ly::NROW, "privileged row must fit in the H/row storage (SObs)");
   const bool joystick = Lo.task == DUCK_TASK_JOYSTICK;
   const float nl = c.noise_level;
   // state row offsets (joystick.py:544-560 / standing.py)
@@ -321,14 +220,14 @@ DK void write_obs_team(const KArgs& A, int lane, Slice<SW> L, const FA& F, const
     const int k = lane;
     const float gyro = L[Ly::SENS + c.sens_gyro + k], acc = L[Ly::SENS + c.sens_accelerometer + k];
     const float grav = -L[Ly::IMUR + k];
-    const float ngrav = grav + (2.0f * r.u(SLOT_GRAVITY + k) - 1.0f) * nl * c.noise_gravity;
+    const float ngrav = grav + (2.0f * r.u(slot_base + SLOT_GRAVITY + k) - 1.0f) * nl * c.noise_gravity;
     // IMU delay history (joystick.py:521-530): shift by one sample, the delayed one is never emitted
     const float h0 = F[Lo.imu_history + k], h1 = F[Lo.imu_history + 3 + k];
     F[Lo.imu_history + 6 + k] = h1;
     F[Lo.imu_history + 3 + k] = h0;
     F[Lo.imu_history + k] = ngrav;
-    out(k, gyro + (2.0f * r.u(SLOT_GYRO + k) - 1.0f) * nl * c.noise_gyro);
-    out(3 + k, acc + (2.0f * r.u(SLOT_ACCEL + k) - 1.0f) * nl * c.noise_accelerometer);
+    out(k, gyro + (2.0f * r.u(slot_base + SLOT_GYRO + k) - 1.0f) * nl * c.noise_gyro);
+    out(3 + k, acc + (2.0f * r.u(slot_base + SLOT_ACCEL + k) - 1.0f) * nl * c.noise_accelerometer);
     out(P + k, gyro);
     out(P + 3 + k, acc);
     out(P + 6 + k, grav);
@@ -343,8 +242,8 @@ DK void write_obs_team(const KArgs& A, int lane, Slice<SW> L, const FA& F, const
     float ja = L[Ly::QPOS + c.actuator_qposadr[a]];
     if (c.backlash_qposadr[a] >= 0) ja += L[Ly::QPOS + c.backlash_qposadr[a]];
     const float jv = L[Ly::QVEL + c.actuator_qveladr[a]];
-    out(OQ + a, ja + (2.0f * r.u(SLOT_QPOS + a) - 1.0f) * nl * c.qpos_noise_scale[a] - c.default_actuator[a]);
-    out(OV + a, (jv + (2.0f * r.u(SLOT_QVEL + a) - 1.0f) * nl * c.noise_joint_vel) * c.dof_vel_scale);
+    out(OQ + a, ja + (2.0f * r.u(slot_base + SLOT_QPOS + a) - 1.0f) * nl * c.qpos_noise_scale[a] - c.default_actuator[a]);
+    out(OV + a, (jv + (2.0f * r.u(slot_base + SLOT_QVEL + a) - 1.0f) * nl * c.noise_joint_vel) * c.dof_vel_scale);
     out(O1 + a, F[Lo.last_act + a]);
     out(O2 + a, F[Lo.last_last_act + a]);
     out(O3 + a, F[Lo.last_last_last_act + a]);
@@ -372,7 +271,9 @@ DK void write_obs_team(const KArgs& A, int lane, Slice<SW> L, const FA& F, const
     for (int k = lane; k < 40; k += TEAM) out(PR + k, F[Lo.ref_motion + k]);
 }
 
-template <class Md, int WG>
+// Joystick.reset / Standing.reset for the masked envs. Every lane of the team runs the serial part
+// (the same values to the same addresses); the forward and the observation rows are split over it
+template <class Md>
 __global__ void __launch_bounds__(TPB) reset_kernel(KArgs A) {
   using Ly = Lay<Md>;
   {
@@ -381,23 +282,22 @@ __global__ void __launch_bounds__(TPB) reset_kernel(KArgs A) {
   }
   int lane;
   const int t = local_env(lane);
-  if (t < 0) return;
-  const int e = blockIdx.x * WG + t;
+  const int e = blockIdx.x * TEAM_WG + t;
   if (e >= A.n) return;
   if (A.mask && !A.mask[e]) return;
   extern __shared__ float lds[];
-  const Slice<SW> L = env_slice<Md>(lds, t);
+  lds_float* const L = env_slice<Md>(lds, t);
   const duck_env_config& c = A.cfg;
   const duck_layout& Lo = A.lay;
   constexpr int NQ = Md::NQ, NV = Md::NV, NU = Md::NU;
-  Col<0> F{A.fs + e, A.n};
+  const Col F{A.fs + e, A.n};
   auto iset = [&](int k, int32_t v) { A.is[(size_t)k * A.n + e] = v; };
   for (int k = 0; k < Lo.nfloat; k++) F[k] = 0.0f;
   for (int k = 0; k < Lo.nint; k++) iset(k, 0);
   Rng r;
   derive_key(A.seed, A.env_offset + e, KEY_TAG_ENV, r.k0, r.k1);
   r.ctr = 0;
-  load_dyn<Md, SW>(A, e, L);
+  load_dyn<Md>(A, e, L);
   // Joystick.reset (joystick.py:206-258)
   for (int i = 0; i < NQ; i++) L[Ly::QPOS + i] = c.init_qpos[i];
   for (int i = 0; i < NV; i++) { L[Ly::QVEL + i] = 0.0f; L[Ly::WARM + i] = 0.0f; }
@@ -433,16 +333,29 @@ __global__ void __launch_bounds__(TPB) reset_kernel(KArgs A) {
     reference_motion(A, cmd[0], cmd[1], cmd[2], 0, ref);
     for (int k = 0; k < 40; k++) F[Lo.ref_motion + k] = ref[k];
   }
+  // the rows go through LDS (the H/row storage is dead after the forward), never back through A.obs:
+  // a lane reads from global memory only what it wrote itself
+  write_obs_team<Md>(A, lane, L, F, SObs{L + Ly::H}, r, RSLOT_OBS, 0);
+  TSYNC();
+  float* priv = A.priv + (size_t)e * Lo.priv_size;
+  float* obs = A.obs + (size_t)e * Lo.obs_size;
+  for (int k = lane; k < Lo.priv_size; k += TEAM) {  // coalesced over the team; state = the row's prefix
+    const float v = L[Ly::H + k];
+    priv[k] = v;
+    F[Lo.first_priv + k] = v;
+    if (k < Lo.obs_size) {
+      obs[k] = v;
+      F[Lo.first_obs + k] = v;
+    }
+  }
+  // the physics state and its snapshot last: stored ahead of the rows, the height-field scenes'
+  // reset_kernel compiles with a split copy in front of an exec restore (tools/isa_exec_check.py)
   for (int i = 0; i < NQ; i++) { F[Lo.qpos + i] = L[Ly::QPOS + i]; F[Lo.first_qpos + i] = L[Ly::QPOS + i]; }
   for (int i = 0; i < NV; i++) {
     F[Lo.qvel + i] = L[Ly::QVEL + i]; F[Lo.first_qvel + i] = L[Ly::QVEL + i];
     F[Lo.qacc_warmstart + i] = L[Ly::WARM + i]; F[Lo.first_qacc_warmstart + i] = L[Ly::WARM + i];
   }
   for (int a = 0; a < NU; a++) { F[Lo.ctrl + a] = L[Ly::CTRL + a]; F[Lo.first_ctrl + a] = L[Ly::CTRL + a]; }
-  write_obs<Md, SW>(A, e, L, F, GObs{A.obs + (size_t)e * Lo.obs_size, A.priv + (size_t)e * Lo.priv_size, Lo.obs_size},
-                    r, RSLOT_OBS, 0);
-  for (int k = 0; k < Lo.obs_size; k++) F[Lo.first_obs + k] = A.obs[(size_t)e * Lo.obs_size + k];
-  for (int k = 0; k < Lo.priv_size; k++) F[Lo.first_priv + k] = A.priv[(size_t)e * Lo.priv_size + k];
 }
 
 // the per-env values step_env reads from HBM besides the hot state: integer counters, the RNG
@@ -472,21 +385,12 @@ DK StepPre step_prefetch(const KArgs& A, int e, int lane) {
   return P;
 }
 
-// for (i = l0; i < N; i += TS) f(i) with the trip count unrolled at compile time (l0 < TS): straight-line
-// code instead of a loop whose trip count depends on the lane (team mode: l0 = lane, TS = TEAM)
-template <int N, int TS, class Fn>
-DK void strided_for(int l0, Fn&& f) {
-#pragma unroll
-  for (int s = 0; s < (N + TS - 1) / TS; s++) {
-    const int i = l0 + TS * s;
-    if (TS * (s + 1) <= N || i < N) f(i);
-  }
-}
-
-// Joystick.step body for env e (joystick.py:323-481 + wrappers); F = the env's hot state
-// (LDS-staged or the global row), G = the global row (auto-reset snapshot)
-template <class Md, class FA, bool STAGE_OBS, class RT, int LAT = 0>
-DK void step_env(const KArgs& A, int e, int lane, Slice<SW> L, const FA& F, const Col<0>& G, const RT& r,
+// Joystick.step body for env e (joystick.py:323-481 + wrappers), run by the env's team: the
+// per-actuator / per-dof loops are split over its lanes and their sums combined by DPP row
+// reductions. F = the env's hot state (LDS-staged or the global row), G = the global row (auto-reset
+// snapshot)
+template <class Md, class FA, class RT, int LAT = 0>
+DK void step_env(const KArgs& A, int e, int lane, lds_float* L, const FA& F, const Col& G, const RT& r,
                  const StepPre& P) {
   using Ly = Lay<Md>;
   const duck_env_config& c = A.cfg;
@@ -517,8 +421,8 @@ DK void step_env(const KArgs& A, int e, int lane, Slice<SW> L, const FA& F, cons
   // action delay (joystick.py:362-376): history = [a_t, a_{t-1}, a_{t-2}]
   const int didx = r.randint(SLOT_ACTION_DELAY, c.action_min_delay, c.action_max_delay);
   float arate = 0.0f;
-  for (int a = STAGE_OBS ? lane : 0; a < NU; a += STAGE_OBS ? TEAM : 1) {
-    const float act = STAGE_OBS ? P.act : A.action[(size_t)e * NU + a];
+  for (int a = lane; a < NU; a += TEAM) {
+    const float act = P.act;
     const float h1 = F[Lo.action_history + a], h2 = F[Lo.action_history + NU + a];
     F[Lo.action_history + a] = act;
     F[Lo.action_history + NU + a] = h1;
@@ -540,22 +444,14 @@ DK void step_env(const KArgs& A, int e, int lane, Slice<SW> L, const FA& F, cons
   // never pushes (XLA integer remainder by zero returns the dividend), and never divides by zero here
   const float gate = (push_interval != 0 && (push_step + 1) % push_interval == 0) ? 1.0f : 0.0f;
   const float push[2] = {cosf(theta) * gate * (float)c.push_enable, sinf(theta) * gate * (float)c.push_enable};
-  if constexpr (STAGE_OBS) {  // team: lane-split copies, sums by DPP
-    arate = tsum(arate);
-    strided_for<NQ, TEAM>(lane, [&](int i) { L[Ly::QPOS + i] = F[Lo.qpos + i]; });
-    strided_for<NV, TEAM>(lane, [&](int i) {
-      L[Ly::QVEL + i] = F[Lo.qvel + i] + (i == 0 ? push[0] * mag : (i == 1 ? push[1] * mag : 0.0f));
-      L[Ly::WARM + i] = F[Lo.qacc_warmstart + i];
-    });
-    load_dyn_team<Md, LAT>(A, e, L, lane);
-    TSYNC();
-  } else {
-    for (int i = 0; i < NQ; i++) L[Ly::QPOS + i] = F[Lo.qpos + i];
-    for (int i = 0; i < NV; i++) { L[Ly::QVEL + i] = F[Lo.qvel + i]; L[Ly::WARM + i] = F[Lo.qacc_warmstart + i]; }
-    L[Ly::QVEL + 0] += push[0] * mag;
-    L[Ly::QVEL + 1] += push[1] * mag;
-    load_dyn<Md, SW>(A, e, L);
-  }
+  arate = tsum(arate);
+  team_for<NQ>(lane, [&](int i) { L[Ly::QPOS + i] = F[Lo.qpos + i]; });
+  team_for<NV>(lane, [&](int i) {
+    L[Ly::QVEL + i] = F[Lo.qvel + i] + (i == 0 ? push[0] * mag : (i == 1 ? push[1] * mag : 0.0f));
+    L[Ly::WARM + i] = F[Lo.qacc_warmstart + i];
+  });
+  load_dyn_team<Md, LAT>(A, e, L, lane);
+  TSYNC();
   // physics (joystick.py:420)
   float* scr = A.scratch ? A.scratch + e : nullptr;
   STAGE_MARK(29);
@@ -566,8 +462,8 @@ DK void step_env(const KArgs& A, int e, int lane, Slice<SW> L, const FA& F, cons
     (void)scr;
     LAT_T(43, 5);
     for (int s = 0; s < c.n_substeps; s++) {
-      if constexpr (LAT == 2) TPL::lat2_a(L.p, lane, s, A.hfield);
-      else TPL::lat_r0(L.p, lane, s);
+      if constexpr (LAT == 2) TPL::lat2_a(L, lane, s, A.hfield);
+      else TPL::lat_r0(L, lane, s);
     }
     TPL::ev_wait(TPL::EV_EULER, c.n_substeps);
     LAT_T(44, 5);
@@ -576,7 +472,7 @@ DK void step_env(const KArgs& A, int e, int lane, Slice<SW> L, const FA& F, cons
       phys_step<Md>(L, lane, true, s == c.n_substeps - 1, nullptr, 0, scr, n, A.hfield);
   }
   STAGE_RESET();
-  for (int a = STAGE_OBS ? lane : 0; a < NU; a += STAGE_OBS ? TEAM : 1) {
+  for (int a = lane; a < NU; a += TEAM) {
     F[Lo.motor_targets + a] = L[Ly::CTRL + a];
     F[Lo.ctrl + a] = L[Ly::CTRL + a];
   }
@@ -586,29 +482,14 @@ DK void step_env(const KArgs& A, int e, int lane, Slice<SW> L, const FA& F, cons
     F[Lo.feet_air_time + k] = F[Lo.feet_air_time + k] + dt;
     F[Lo.swing_peak + k] = fmaxf(F[Lo.swing_peak + k], L[Ly::FOOTZ + k]);
   }
-  if constexpr (STAGE_OBS) {
-    static_assert(DUCK_OBS_SIZE(NU) + 15 + 3 * NU + 1 + 2 + 6 + 2 + 40 + 1 + 2 <= Ly::SCR_OBS && Ly::SCR_OBS <= Ly::HSZ + 4 * Ly::NROW,
-                  "privileged row must fit in the H/row storage");
-    write_obs_team<Md>(A, lane, L, F, SObs<SW>{L, Ly::H}, r, imitation_i);
-    TSYNC();
-  } else {
-    write_obs<Md, SW>(A, e, L, F, GObs{A.obs + (size_t)e * Lo.obs_size, A.priv + (size_t)e * Lo.priv_size, Lo.obs_size},
-                      r, 0, imitation_i);
-  }
+  write_obs_team<Md>(A, lane, L, F, SObs{L + Ly::H}, r, 0, imitation_i);
+  TSYNC();
   STAGE_MARK(30);
-  // team mode: the per-actuator / per-dof loops below are split over the team's lanes and
-  // their sums combined by DPP row reductions (single-lane mode: TS = 1, plain loops)
-  constexpr int TS = STAGE_OBS ? TEAM : 1;
-  const int l0 = STAGE_OBS ? lane : 0;
-  auto red = [&](float v) {
-    if constexpr (STAGE_OBS) return tsum(v);
-    else return v;
-  };
   // termination (joystick.py:483-485)
   float nanp = 0.0f;
-  strided_for<NQ, TS>(l0, [&](int i) { nanp += isnan(L[Ly::QPOS + i]) ? 1.0f : 0.0f; });
-  strided_for<NV, TS>(l0, [&](int i) { nanp += isnan(L[Ly::QVEL + i]) ? 1.0f : 0.0f; });
-  const bool nan = red(nanp) > 0.0f;
+  team_for<NQ>(lane, [&](int i) { nanp += isnan(L[Ly::QPOS + i]) ? 1.0f : 0.0f; });
+  team_for<NV>(lane, [&](int i) { nanp += isnan(L[Ly::QVEL + i]) ? 1.0f : 0.0f; });
+  const bool nan = tsum(nanp) > 0.0f;
   float done = (L[Ly::SENS + c.sens_upvector + 2] < 0.0f || nan) ? 1.0f : 0.0f;
   // rewards (joystick.py:622-669, common/rewards.py:11-125, custom_rewards.py:4-148)
   float cmd[7];
@@ -622,7 +503,7 @@ DK void step_env(const KArgs& A, int e, int lane, Slice<SW> L, const FA& F, cons
   const float r_ang = nan_to_num(expf(-((cmd[2] - gz) * (cmd[2] - gz)) / sigma));
   const bool standing = Lo.task == DUCK_TASK_STANDING;
   float torq = 0.0f, pc = 0.0f, vc = 0.0f, lpc = 0.0f, lvc = 0.0f, hp = 0.0f;
-  for (int a = l0; a < NU; a += TS) {
+  for (int a = lane; a < NU; a += TEAM) {
     const float f = L[Ly::AF + a];
     const float q = L[Ly::QPOS + c.actuator_qposadr[a]], qd = fabsf(L[Ly::QVEL + c.actuator_qveladr[a]]);
     const float dq = fabsf(q - c.default_actuator[a]);
@@ -639,9 +520,9 @@ DK void step_env(const KArgs& A, int e, int lane, Slice<SW> L, const FA& F, cons
       }
     }
   }
-  torq = red(torq);
-  pc = red(pc);
-  vc = red(vc);
+  torq = tsum(torq);
+  pc = tsum(pc);
+  vc = tsum(vc);
   const float cn = sqrtf(cmd[0] * cmd[0] + cmd[1] * cmd[1] + cmd[2] * cmd[2]);
   const float r_still = nan_to_num(pc + vc) * (cn < 0.01f ? 1.0f : 0.0f);
   float imit = 0.0f;
@@ -657,7 +538,7 @@ DK void step_env(const KArgs& A, int e, int lane, Slice<SW> L, const FA& F, cons
     const float lin_xy = expf(-8.0f * lxy), lin_z = expf(-8.0f * dz * dz);
     const float ang_xy = expf(-2.0f * axy) * 0.5f, ang_z = expf(-2.0f * dwz * dwz) * 0.5f;
     float jp = 0.0f, jv = 0.0f;
-    for (int k = l0; k < 5; k += TS) {
+    for (int k = lane; k < 5; k += TEAM) {
       const float q1 = L[Ly::QPOS + c.actuator_qposadr[k]] - F[R0 + k];
       const float q2 = L[Ly::QPOS + c.actuator_qposadr[NU - 5 + k]] - F[R0 + 11 + k];
       const float v1 = L[Ly::QVEL + c.actuator_qveladr[k]] - F[R0 + 16 + k];
@@ -665,8 +546,8 @@ DK void step_env(const KArgs& A, int e, int lane, Slice<SW> L, const FA& F, cons
       jp += q1 * q1 + q2 * q2;
       jv += v1 * v1 + v2 * v2;
     }
-    jp = red(jp);
-    jv = red(jv);
+    jp = tsum(jp);
+    jv = tsum(jv);
     float contact_r = 0.0f;
     for (int k = 0; k < 2; k++) contact_r += (con[k] == (F[R0 + 32 + k] > 0.5f ? 1.0f : 0.0f)) ? 1.0f : 0.0f;
     float rr = lin_xy + lin_z + ang_xy + ang_z + (-jp * 15.0f) + (-jv * 1e-3f) + contact_r;
@@ -677,9 +558,9 @@ DK void step_env(const KArgs& A, int e, int lane, Slice<SW> L, const FA& F, cons
   if (standing) {
     // Standing._get_reward (standing.py:584-606): orientation, torques, action_rate, alive,
     // stand_still(ignore_head=True), head_pos (common/rewards.py:45-46,93-117,131-147)
-    lpc = red(lpc);
-    lvc = red(lvc);
-    hp = red(hp);
+    lpc = tsum(lpc);
+    lvc = tsum(lvc);
+    hp = tsum(hp);
     const float ux = L[Ly::SENS + c.sens_upvector], uy = L[Ly::SENS + c.sens_upvector + 1];
     terms[0] = nan_to_num(ux * ux + uy * uy) * c.scale_orientation;
     terms[1] = nan_to_num(torq) * c.scale_torques;
@@ -705,7 +586,7 @@ DK void step_env(const KArgs& A, int e, int lane, Slice<SW> L, const FA& F, cons
   F[Lo.push + 1] = push[1];
   int step = step_prev + 1;
   iset(Lo.push_step, push_step + 1);
-  strided_for<NU, TS>(l0, [&](int a) {
+  team_for<NU>(lane, [&](int a) {
     F[Lo.last_last_last_act + a] = F[Lo.last_last_act + a];
     F[Lo.last_last_act + a] = F[Lo.last_act + a];
     F[Lo.last_act + a] = F[Lo.action_history + a];  // this step's action
@@ -744,19 +625,14 @@ DK void step_env(const KArgs& A, int e, int lane, Slice<SW> L, const FA& F, cons
     iset(Lo.ep_steps, ep_steps);
   }
   if (restore) {
-    for (int i = l0; i < NQ; i += TS) F[Lo.qpos + i] = G[Lo.first_qpos + i];
-    for (int i = l0; i < NV; i += TS) { F[Lo.qvel + i] = G[Lo.first_qvel + i]; F[Lo.qacc_warmstart + i] = G[Lo.first_qacc_warmstart + i]; }
-    for (int a = l0; a < NU; a += TS) F[Lo.ctrl + a] = G[Lo.first_ctrl + a];
-    if constexpr (STAGE_OBS) {
-      TSYNC();
-      for (int k = lane; k < Lo.priv_size; k += TEAM) L[Ly::H + k] = G[Lo.first_priv + k];  // state = its prefix
-    } else {
-      for (int k = 0; k < Lo.obs_size; k++) A.obs[(size_t)e * Lo.obs_size + k] = G[Lo.first_obs + k];
-      for (int k = 0; k < Lo.priv_size; k++) A.priv[(size_t)e * Lo.priv_size + k] = G[Lo.first_priv + k];
-    }
+    for (int i = lane; i < NQ; i += TEAM) F[Lo.qpos + i] = G[Lo.first_qpos + i];
+    for (int i = lane; i < NV; i += TEAM) { F[Lo.qvel + i] = G[Lo.first_qvel + i]; F[Lo.qacc_warmstart + i] = G[Lo.first_qacc_warmstart + i]; }
+    for (int a = lane; a < NU; a += TEAM) F[Lo.ctrl + a] = G[Lo.first_ctrl + a];
+    TSYNC();
+    for (int k = lane; k < Lo.priv_size; k += TEAM) L[Ly::H + k] = G[Lo.first_priv + k];  // state = its prefix
   } else {
-    strided_for<NQ, TS>(l0, [&](int i) { F[Lo.qpos + i] = L[Ly::QPOS + i]; });
-    strided_for<NV, TS>(l0, [&](int i) { F[Lo.qvel + i] = L[Ly::QVEL + i]; F[Lo.qacc_warmstart + i] = L[Ly::WARM + i]; });
+    team_for<NQ>(lane, [&](int i) { F[Lo.qpos + i] = L[Ly::QPOS + i]; });
+    team_for<NV>(lane, [&](int i) { F[Lo.qvel + i] = L[Ly::QVEL + i]; F[Lo.qacc_warmstart + i] = L[Ly::WARM + i]; });
   }
   F[Lo.reward] = reward;
   F[Lo.done] = done;
@@ -764,36 +640,46 @@ DK void step_env(const KArgs& A, int e, int lane, Slice<SW> L, const FA& F, cons
   A.reward[e] = reward;
   A.done[e] = done;
   STAGE_MARK(31);
-  if constexpr (STAGE_OBS) {  // coalesced rows: lane k of the team stores elements k, k + 16, ...
-    TSYNC();
-    float* priv = A.priv + (size_t)e * Lo.priv_size;
-    float* obs = A.obs + (size_t)e * Lo.obs_size;
-    // the staged row is read in one batch (compile-time trip count over the largest row), then
-    // stored: one LDS round trip instead of one per element group; obs is the row's prefix
-    constexpr int PMAX = DUCK_OBS_SIZE(NU) + 15 + 3 * NU + 1 + 2 + 6 + 2 + 40 + 1 + 2;
-    constexpr int NKP = (PMAX + TEAM - 1) / TEAM, NKO = (DUCK_OBS_SIZE(NU) + TEAM - 1) / TEAM;
-    float pv[NKP];
+  // coalesced rows: lane k of the team stores elements k, k + 16, ...
+  TSYNC();
+  float* priv = A.priv + (size_t)e * Lo.priv_size;
+  float* obs = A.obs + (size_t)e * Lo.obs_size;
+  // the staged row is read in one batch (compile-time trip count over the longest row), then
+  // stored: one LDS round trip instead of one per element group; obs is the row's prefix
+  constexpr int PMAX = priv_row_max(NU);
+  constexpr int NKP = (PMAX + TEAM - 1) / TEAM, NKO = (DUCK_OBS_SIZE(NU) + TEAM - 1) / TEAM;
+  float pv[NKP];
 #pragma unroll
-    for (int kk = 0; kk < NKP; kk++) {
-      const int k = lane + TEAM * kk;
-      pv[kk] = L[Ly::H + (k < PMAX ? k : PMAX - 1)];
-    }
+  for (int kk = 0; kk < NKP; kk++) {
+    const int k = lane + TEAM * kk;
+    pv[kk] = L[Ly::H + (k < PMAX ? k : PMAX - 1)];
+  }
 #pragma unroll
-    for (int kk = 0; kk < NKP; kk++) {
-      const int k = lane + TEAM * kk;
-      if (k < Lo.priv_size) priv[k] = pv[kk];
-    }
+  for (int kk = 0; kk < NKP; kk++) {
+    const int k = lane + TEAM * kk;
+    if (k < Lo.priv_size) priv[k] = pv[kk];
+  }
 #pragma unroll
-    for (int kk = 0; kk < NKO; kk++) {
-      const int k = lane + TEAM * kk;
-      if (k < Lo.obs_size) obs[k] = pv[kk];
-    }
+  for (int kk = 0; kk < NKO; kk++) {
+    const int k = lane + TEAM * kk;
+    if (k < Lo.obs_size) obs[k] = pv[kk];
   }
   STAGE_MARK(34);
 }
 
+// the step's random stream: key and counter from the prefetch, the first RngTab::N draws made by
+// the team in parallel into tab (a TSYNC before the first draw is read)
+DK RngTab step_rng(const StepPre& P, lds_float* tab, int lane) {
+  RngTab rt;
+  rt.k0 = P.k0;
+  rt.k1 = P.k1;
+  rt.ctr = P.ctr;
+  rt.tab = tab;
+  rt.fill(tab, lane);
+  return rt;
+}
 
-template <class Md, int WG>
+template <class Md>
 __global__ void __launch_bounds__(TPB) step_kernel(KArgs A) {
   STAGE_T0();
 #ifdef DUCK_ANY_PROF
@@ -807,77 +693,72 @@ __global__ void __launch_bounds__(TPB) step_kernel(KArgs A) {
   STAGE_MARK(14);
   int lane;
   const int t = local_env(lane);
-  if (t < 0) return;
-  const int e = blockIdx.x * WG + t;
+  const int e = blockIdx.x * TEAM_WG + t;
   const int n = A.n;
   extern __shared__ float lds[];
   if constexpr (TL::ES_LDS) {
     // hot state <-> LDS by the whole workgroup, field-major: a wave instruction moves 4 fields
     // x 16 consecutive envs (four 64-B segments of the [field][env] rows) instead of 16 fields x
-    // 4 envs; the step's 64 random draws are made by each team in parallel into the same region
-    const int j = threadIdx.x % WG, ej = blockIdx.x * WG + j;
+    // 4 envs; the step's 64 random draws are made by each team in parallel into the same region.
+    // (The four staging blocks, here and in step_lat_body, stay written out: moved into a shared
+    // inline helper they compile to different step kernels.)
+    const int j = threadIdx.x % TEAM_WG, ej = blockIdx.x * TEAM_WG + j;
     lds_float* esj = (lds_float*)(lds + TL::ES + j * TL::ESTRIDE);
     const StepPre P = step_prefetch<Md>(A, e, lane);
     {
       // compile-time trip count: all of the thread's loads are in flight before the first store
       // waits (one memory round trip; a runtime-bounded loop costs one per unrolled group)
-      constexpr int NK = (TL::HOT + TPB / WG - 1) / (TPB / WG);
+      constexpr int NK = (TL::HOT + TPB / TEAM_WG - 1) / (TPB / TEAM_WG);
       const int ejc = ej < n ? ej : 0;
       float hv[NK];
 #pragma unroll
       for (int kk = 0; kk < NK; kk++) {
-        const int k = (int)threadIdx.x / WG + (TPB / WG) * kk;
+        const int k = (int)threadIdx.x / TEAM_WG + (TPB / TEAM_WG) * kk;
         hv[kk] = A.fs[(size_t)(k < TL::HOT ? k : TL::HOT - 1) * n + ejc];
       }
 #pragma unroll
       for (int kk = 0; kk < NK; kk++) {
-        const int k = (int)threadIdx.x / WG + (TPB / WG) * kk;
+        const int k = (int)threadIdx.x / TEAM_WG + (TPB / TEAM_WG) * kk;
         if (ej < n && k < TL::HOT) esj[k] = hv[kk];
       }
     }
     __syncthreads();
     STAGE_MARK(32);
     if (e < n) {
-      const Slice<SW> L = env_slice<Md>(lds, t);
-      const Col<0> G{A.fs + e, n};  // global row: the auto-reset snapshot (first_*) stays in HBM
-      const duck_layout& Lo = A.lay;
+      lds_float* const L = env_slice<Md>(lds, t);
+      const Col G{A.fs + e, n};  // global row: the auto-reset snapshot (first_*) stays in HBM
       lds_float* esp = (lds_float*)(lds + TL::ES + t * TL::ESTRIDE);
-      RngTab rt;
-      rt.k0 = P.k0;
-      rt.k1 = P.k1;
-      rt.ctr = P.ctr;
-      rt.tab = esp + TL::HOT;
-      rt.fill(esp + TL::HOT, lane);
+      const RngTab rt = step_rng(P, esp + TL::HOT, lane);
       TSYNC();
       STAGE_MARK(33);
-      step_env<Md, LCol, true>(A, e, lane, L, LCol{esp}, G, rt, P);
+      step_env<Md>(A, e, lane, L, LCol{esp}, G, rt, P);
       STAGE_RESET();
     }
     __syncthreads();
     {
-      constexpr int NK = (TL::HOT + TPB / WG - 1) / (TPB / WG);
+      constexpr int NK = (TL::HOT + TPB / TEAM_WG - 1) / (TPB / TEAM_WG);
       float hv[NK];
 #pragma unroll
       for (int kk = 0; kk < NK; kk++) {
-        const int k = (int)threadIdx.x / WG + (TPB / WG) * kk;
+        const int k = (int)threadIdx.x / TEAM_WG + (TPB / TEAM_WG) * kk;
         hv[kk] = esj[k < TL::HOT ? k : TL::HOT - 1];
       }
 #pragma unroll
       for (int kk = 0; kk < NK; kk++) {
-        const int k = (int)threadIdx.x / WG + (TPB / WG) * kk;
+        const int k = (int)threadIdx.x / TEAM_WG + (TPB / TEAM_WG) * kk;
         if (ej < n && k < TL::HOT) A.fs[(size_t)k * n + ej] = hv[kk];
       }
     }
   } else {
     if (e >= n) return;
-    const Slice<SW> L = env_slice<Md>(lds, t);
-    const Col<0> G{A.fs + e, n};
+    lds_float* const L = env_slice<Md>(lds, t);
+    const Col G{A.fs + e, n};
     const duck_layout& Lo = A.lay;
     Rng r;
     r.k0 = (uint32_t)A.is[(size_t)Lo.rng_key * n + e];
     r.k1 = (uint32_t)A.is[(size_t)(Lo.rng_key + 1) * n + e];
     r.ctr = (uint32_t)A.is[(size_t)Lo.rng_ctr * n + e];
-    step_env<Md, Col<0>, true>(A, e, lane, L, G, G, r, step_prefetch<Md>(A, e, lane));
+    step_env<Md>(A, e, lane, L, G, G, r, step_prefetch<Md>(A, e, lane));
     STAGE_RESET();  // (no staged hot state to store: mark 15 counts nothing on this path)
   }
   STAGE_MARK(15);
@@ -938,20 +819,15 @@ __device__ __forceinline__ void step_lat_body(KArgs A) {
   __syncthreads();
   LAT_T(42, 5);
   if (e < n) {
-    const Slice<SW> L = env_slice<Md, LAT>(lds, t);
+    lds_float* const L = env_slice<Md, LAT>(lds, t);
     const int ns = A.cfg.n_substeps;
     float* scr = A.scratch ? A.scratch + e : nullptr;
     auto env_code = [&]() {
-      const Col<0> G{A.fs + e, n};
+      const Col G{A.fs + e, n};
       lds_float* esp = (lds_float*)(lds + TL::ES + t * TL::ESTRIDE);
-      RngTab rt;
-      rt.k0 = P.k0;
-      rt.k1 = P.k1;
-      rt.ctr = P.ctr;
-      rt.tab = esp + TL::HOT;
-      rt.fill(esp + TL::HOT, lane);
+      const RngTab rt = step_rng(P, esp + TL::HOT, lane);
       TSYNC();
-      step_env<Md, LCol, true, RngTab, LAT>(A, e, lane, L, LCol{esp}, G, rt, P);
+      step_env<Md, LCol, RngTab, LAT>(A, e, lane, L, LCol{esp}, G, rt, P);
       LAT_T(45, 5);
     };
     if constexpr (LAT == 2) {
@@ -959,17 +835,17 @@ __device__ __forceinline__ void step_lat_body(KArgs A) {
       if ((wave & 1) == 0) {
         env_code();
       } else {
-        for (int s = 0; s < ns; s++) TPL::lat2_b(L.p, lane, s, true, s == ns - 1, scr, n);
+        for (int s = 0; s < ns; s++) TPL::lat2_b(L, lane, s, true, s == ns - 1, scr, n);
       }
     } else {
       if (wave == 0) {
         env_code();
       } else if (wave == 1) {
-        for (int s = 0; s < ns; s++) TPL::lat_r1(L.p, lane, s, true, s == ns - 1, scr, n);
+        for (int s = 0; s < ns; s++) TPL::lat_r1(L, lane, s, true, s == ns - 1, scr, n);
       } else if (wave == 2) {
-        for (int s = 0; s < ns; s++) TPL::lat_r2(L.p, lane, s, A.hfield);
+        for (int s = 0; s < ns; s++) TPL::lat_r2(L, lane, s, A.hfield);
       } else {
-        for (int s = 0; s < ns; s++) TPL::lat_r3(L.p, lane, s);
+        for (int s = 0; s < ns; s++) TPL::lat_r3(L, lane, s);
       }
     }
   }
@@ -1027,7 +903,7 @@ __global__ void __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(2, 2))
   if constexpr (LatX2<Md>::PAYS) step_lat_body<Md, LAT_X2>(A);
 }
 
-template <class Md, int WG>
+template <class Md>
 __global__ void __launch_bounds__(TPB) physics_kernel(KArgs A, float* qpos_g, float* qvel_g, float* warm_g,
                                                      const float* ctrl_g, int nsub, float* aux) {
   using Ly = Lay<Md>;
@@ -1037,16 +913,15 @@ __global__ void __launch_bounds__(TPB) physics_kernel(KArgs A, float* qpos_g, fl
   }
   int lane;
   const int t = local_env(lane);
-  if (t < 0) return;
-  const int e = blockIdx.x * WG + t;
+  const int e = blockIdx.x * TEAM_WG + t;
   const int n = A.n;
   if (e >= n) return;
   extern __shared__ float lds[];
-  const Slice<SW> L = env_slice<Md>(lds, t);
+  lds_float* const L = env_slice<Md>(lds, t);
   for (int i = 0; i < Md::NQ; i++) L[Ly::QPOS + i] = qpos_g[(size_t)i * n + e];
   for (int i = 0; i < Md::NV; i++) { L[Ly::QVEL + i] = qvel_g[(size_t)i * n + e]; L[Ly::WARM + i] = warm_g[(size_t)i * n + e]; }
   for (int a = 0; a < Md::NU; a++) L[Ly::CTRL + a] = ctrl_g[(size_t)a * n + e];
-  load_dyn<Md, SW>(A, e, L);
+  load_dyn<Md>(A, e, L);
   float* ax = aux ? aux + e : nullptr;
   float* scr = A.scratch ? A.scratch + e : nullptr;
   // nsub = 0: one forward (mjx.forward), no integration
@@ -1097,7 +972,6 @@ static bool matches(const duck_model_desc* m) {
 
 template <class Md>
 static size_t lds_bytes() {
-  static_assert(WG == TEAM_WG, "team workgroup size");
   return (size_t)TLay<Md>::LDS_FLOATS * sizeof(float);
 }
 // 0 = the split does not fit this model's LDS and is not compiled (TLay::FITS)
@@ -1139,8 +1013,8 @@ static int launch_reset(duck_sim* s, int n, float* fs, int32_t* is, const uint8_
   KArgs A = make_args(s, n);
   A.fs = fs; A.is = is; A.mask = mask; A.seed = seed; A.env_offset = env_offset; A.dr = dr;
   A.obs = obs; A.priv = priv;
-  const dim3 grid((A.n + WG - 1) / WG), block(TPB);
-  hipLaunchKernelGGL((reset_kernel<Md, WG>), grid, block, lds_bytes<Md>(), st, A);
+  const dim3 grid((A.n + TEAM_WG - 1) / TEAM_WG), block(TPB);
+  hipLaunchKernelGGL((reset_kernel<Md>), grid, block, lds_bytes<Md>(), st, A);
   HIPCHECK(hipGetLastError());
   return DUCK_OK;
 }
@@ -1179,8 +1053,8 @@ static int launch_step(duck_sim* s, int n, float* fs, int32_t* is, const float* 
     HIPCHECK(hipGetLastError());
     return DUCK_OK;
   }
-  const dim3 grid((A.n + WG - 1) / WG), block(TPB);
-  hipLaunchKernelGGL((step_kernel<Md, WG>), grid, block, lds_bytes<Md>(), st, A);
+  const dim3 grid((A.n + TEAM_WG - 1) / TEAM_WG), block(TPB);
+  hipLaunchKernelGGL((step_kernel<Md>), grid, block, lds_bytes<Md>(), st, A);
   HIPCHECK(hipGetLastError());
   return DUCK_OK;
 }
@@ -1196,11 +1070,11 @@ static int launch_randomize(duck_sim* s, int n, float* dr, uint64_t seed, int64_
 template <class Md>
 static int launch_physics(duck_sim* s, int n, float* qpos, float* qvel, float* warm, const float* ctrl, const float* dr,
                           int nsub, float* aux, float* scratch, hipStream_t st) {
-  const dim3 grid((n + WG - 1) / WG), block(TPB);
+  const dim3 grid((n + TEAM_WG - 1) / TEAM_WG), block(TPB);
   KArgs A = make_args(s, n);
   A.dr = dr;
   A.scratch = scratch;
-  hipLaunchKernelGGL((physics_kernel<Md, WG>), grid, block, lds_bytes<Md>(), st, A, qpos, qvel, warm, ctrl, nsub, aux);
+  hipLaunchKernelGGL((physics_kernel<Md>), grid, block, lds_bytes<Md>(), st, A, qpos, qvel, warm, ctrl, nsub, aux);
   HIPCHECK(hipGetLastError());
   return DUCK_OK;
 }

@@ -4,12 +4,13 @@
 // smooth acceleration -> collision -> constraint rows -> MJX Newton -> sensors -> Euler) is the
 // 16-lane team implementation in duck_team.h. This header holds what it builds on: the per-env LDS
 // slice layout (Lay), the impedance law (kbi), the plane/convex manifold helpers, and a few per-env
-// helpers (Phys). The round-1 single-lane debug build (one env per lane, -DDUCK_TEAM=0) is retired.
+// helpers (Phys).
 //
 // Contact Jacobians are never materialised: a contact row is a 6-vector a = [r x u; u]
 // in the foot's com-based spatial frame, J.x = a . (sum_chain cdof_i x_i), and J'DJ is
 // accumulated as one 6x6 block per foot projected onto the foot's dof chain.
 #pragma once
+#include "../../include/duck_env.h"
 #include "duck_math.h"
 
 #define DNI __device__ __noinline__
@@ -85,13 +86,11 @@ static __device__ unsigned long long g_stage_wg[DUCK_NSTAGE * 256];
   } while (0)
 #endif
 
-template <int WG>
-struct Slice {
-  lds_float* p;
-  DK lds_float& operator[](int k) const { return p[k * WG]; }
-};
+// the longest privileged observation row (Joystick with imitation: duck_layout_make's priv_size);
+// the state row is its prefix (write_obs_team, duck_env_kernels.h)
+constexpr int priv_row_max(int nu) { return DUCK_OBS_SIZE(nu) + 15 + 3 * nu + 1 + 2 + 6 + 2 + 40 + 1 + 2; }
 
-// Per-lane LDS layout (floats)
+// Per-env LDS slice layout (floats); a slice is contiguous and addressed through an lds_float*
 template <class Md>
 struct Lay {
   static constexpr int NB = Md::NB, NV = Md::NV, NQ = Md::NQ, NU = Md::NU;
@@ -116,20 +115,16 @@ struct Lay {
   // the rows (the Newton Hessian itself is assembled in registers, never stored). Its users, each
   // from H on: the tree passes' scratch (rne: 12 NB + 6 NV), the hull/hull SAT's edge tables (6 per
   // hull edge and face), the height-field survivor queue (16 entries of 28 per env slice + 16-B
-  // alignment), the staged privileged observation row (env code, 86 + 9 NU). H is sized so that
+  // alignment), the staged privileged observation row (env code, priv_row_max). H is sized so that
   // H + rows covers the largest of them: the rows alone cover most, so H is short (the backlash
   // scenes' slices then leave LDS for the model blob: TLay::TAB_LDS).
   static constexpr int SCR_TREE = 12 * NB + 6 * NV, SCR_SAT = 6 * (Md::NHE + Md::NHF);
-  static constexpr int SCR_HF = Md::FLOOR_TYPE == 1 ? 3 + 28 * 16 : 0, SCR_OBS = 86 + 9 * NU;
+  static constexpr int SCR_HF = Md::FLOOR_TYPE == 1 ? 3 + 28 * 16 : 0, SCR_OBS = priv_row_max(NU);
   static constexpr int cmax(int a, int b) { return a > b ? a : b; }
   static constexpr int SCR_NEED = cmax(cmax(SCR_TREE, SCR_SAT), cmax(SCR_HF, SCR_OBS));
-  static constexpr int NROWS = NROW;
-  static constexpr int HSZ = ((cmax(SCR_NEED - 4 * NROWS - Md::NLIM, 0) + 3) / 4) * 4;
-  // RNE accumulators live in the H + row storage (dead until smooth()/make_rows())
-  static constexpr int CACC = H, CFRC = CACC + 6 * NB;
-  static_assert(12 * NB <= HSZ + 4 * NROW, "RNE scratch must fit in H + rows");
-  static constexpr int JA = H + HSZ, JV = JA + NROWS, RD = JV + NROWS, AREF = RD + NROWS;
-  static constexpr int LSGN = AREF + NROWS;
+  static constexpr int HSZ = ((cmax(SCR_NEED - 4 * NROW - Md::NLIM, 0) + 3) / 4) * 4;
+  static constexpr int JA = H + HSZ, JV = JA + NROW, RD = JV + NROW, AREF = RD + NROW;
+  static constexpr int LSGN = AREF + NROW;
   static constexpr int CR = LSGN + Md::NLIM, CFR = CR + 3 * NCON, CDIST = CFR + 9 * NCON;
   // Newton 6x6 foot blocks live in CIN's storage (composite inertias are dead after crb())
   static constexpr int KL = CIN, KR = KL + 21, KLR = KR + 21, FL = KLR + 36, FR = FL + 6;
@@ -265,17 +260,16 @@ DK constexpr int cgeom_slot(int g) {
   return g == Md::FLOOR_GEOM ? 0 : (g == Md::LFOOT_GEOM ? 1 : 2);
 }
 
-// Per-env helpers shared with the team kernels (duck_team.h): nominal per-env model values, collision
-// geom frames, contact records, contact point velocity, the debug aux record.
-template <class Md, int WG>
+// Per-env helpers of the team kernels (duck_team.h) and the env kernels: nominal per-env model
+// values, collision geom frames, contact records, contact point velocity, the debug aux record.
+template <class Md>
 struct Phys {
   using Ly = Lay<Md>;
-  using S = Slice<WG>;
   static constexpr int NV = Md::NV, NB = Md::NB, NQ = Md::NQ, NU = Md::NU;
   static constexpr int NCON = Ly::NCON;
 
   // ---------------- per-env model values ----------------
-  static DK void set_nominal(S L) {
+  static DK void set_nominal(lds_float* L) {
 #pragma unroll
     for (int b = 0; b < NB; b++) L[Ly::DMASS + b] = Md::body_mass[b];
 #pragma unroll
@@ -289,7 +283,7 @@ struct Phys {
   }
 
   // ---------------- collision (mjx collision_driver, 4 slots per pair) ----------------
-  static DK void geom_frame(S L, int g, float* gp, float* gR) {
+  static DK void geom_frame(lds_float* L, int g, float* gp, float* gR) {
     const int b = Md::cgeom_body[g];
     if (Md::body_weldid[b] == 0) {
       float bq[4] = {Md::body_quat[b][0], Md::body_quat[b][1], Md::body_quat[b][2], Md::body_quat[b][3]}, BR[9], t[3];
@@ -309,7 +303,7 @@ struct Phys {
     }
   }
 
-  static DK void store_contact(S L, int slot, float dist, const float* pos, const float* fr) {
+  static DK void store_contact(lds_float* L, int slot, float dist, const float* pos, const float* fr) {
     L[Ly::CDIST + slot] = dist;
 #pragma unroll
     for (int a = 0; a < 3; a++) L[Ly::CR + 3 * slot + a] = pos[a] - L[Ly::COM + a];
@@ -326,7 +320,7 @@ struct Phys {
 
   // debug record: qacc, qacc_smooth, qvel (pre-integration), qfrc_smooth, actuator_force,
   // sensordata, con_dist, con_pos, con_normal, M
-  static DNI void write_aux(S L, float* aux, int stride) {
+  static DNI void write_aux(lds_float* L, float* aux, int stride) {
     int o = 0;
     for (int i = 0; i < NV; i++) aux[(o++) * stride] = L[Ly::QACC + i];
     for (int i = 0; i < NV; i++) aux[(o++) * stride] = L[Ly::QSM + i];

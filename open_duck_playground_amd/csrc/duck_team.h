@@ -1,6 +1,6 @@
 // duck_team.h — mjx.step with a team of 16 lanes per env (CDNA4, fp32).
 //
-// Same physics, same LDS layout (Lay<Md>) and same arithmetic as duck_physics.h, but each
+// The per-env LDS layout (Lay<Md>) and a few per-env helpers come from duck_physics.h. Each
 // env is worked by 16 consecutive lanes of a wave (4 envs per wave, 4 waves per CU at
 // 16 envs per CU): lanes split every stage's independent items — bodies of one tree level,
 // degrees of freedom, mass-matrix entries, LDL' updates of one pivot, hull vertices,
@@ -19,7 +19,7 @@
 
 constexpr int TEAM = 16;
 constexpr int TEAM_WG = 16;  // envs (teams) per workgroup: 256 threads = 4 waves
-constexpr int TPB_TEAM = TEAM * TEAM_WG;
+constexpr int TPB = TEAM * TEAM_WG;  // the block size of every env kernel
 typedef __attribute__((address_space(3))) int lds_int;
 typedef float f4v __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) f4v lds_f4;
@@ -359,31 +359,31 @@ DK void load_model_tables(float* lds) {
     // a compile-time trip count: every load of the thread is issued before the first store waits
     // (a runtime-bounded loop waits for each group of loads: one memory round trip per group)
     int* dst = (int*)(lds + TLy::TAB);
-    constexpr int NK = (Md::NBLOB + TPB_TEAM - 1) / TPB_TEAM;
+    constexpr int NK = (Md::NBLOB + TPB - 1) / TPB;
     int w[NK];
 #pragma unroll
     for (int kk = 0; kk < NK; kk++) {
-      const int i = (int)threadIdx.x + TPB_TEAM * kk;
+      const int i = (int)threadIdx.x + TPB * kk;
       w[kk] = Md::t_blob()[i < Md::NBLOB ? i : Md::NBLOB - 1];
     }
 #pragma unroll
     for (int kk = 0; kk < NK; kk++) {
-      const int i = (int)threadIdx.x + TPB_TEAM * kk;
+      const int i = (int)threadIdx.x + TPB * kk;
       if (i < Md::NBLOB) dst[i] = w[kk];
     }
     __syncthreads();
   } else if constexpr (TLy::HT_LDS) {
     int* dst = (int*)(lds + TLy::TAB);
-    constexpr int N = TLy::NHT, NK = (N + TPB_TEAM - 1) / TPB_TEAM;
+    constexpr int N = TLy::NHT, NK = (N + TPB - 1) / TPB;
     int w[NK];
 #pragma unroll
     for (int kk = 0; kk < NK; kk++) {
-      const int i = (int)threadIdx.x + TPB_TEAM * kk;
+      const int i = (int)threadIdx.x + TPB * kk;
       w[kk] = Md::t_blob()[Md::B_HFACE + (i < N ? i : N - 1)];
     }
 #pragma unroll
     for (int kk = 0; kk < NK; kk++) {
-      const int i = (int)threadIdx.x + TPB_TEAM * kk;
+      const int i = (int)threadIdx.x + TPB * kk;
       if (i < N) dst[i] = w[kk];
     }
     __syncthreads();
@@ -418,8 +418,7 @@ template <class Md, int LAT = 0>
 struct TPhys {
   using Ly = Lay<Md>;
   using TL = TLay<Md, LAT>;
-  using P1 = Phys<Md, 1>;
-  using S1 = Slice<1>;
+  using Ph = Phys<Md>;
   typedef lds_float* LP;
   static constexpr int NV = Md::NV, NB = Md::NB, NQ = Md::NQ, NU = Md::NU, NJ = Md::NJ;
   static constexpr int NCON = Ly::NCON, NFRIC = Md::NFRIC, NLIM = Md::NLIM, NROW = Ly::NROW;
@@ -1541,8 +1540,7 @@ struct TPhys {
     const int p = Md::PLANE_PAIR[0] * (1 - h) + Md::PLANE_PAIR[1] * h;
     const int gs = cgeom_slot<Md>(Md::pair_geom2[p]);
     float pp[3], PR[9], cp[3], CR[9];
-    S1 Ls{L};
-    P1::geom_frame(Ls, 0, pp, PR);
+    Ph::geom_frame(L, 0, pp, PR);
     cgeom_frame(L, gs, cp, CR);
     const float n[3] = {PR[2], PR[5], PR[8]};
     const float dif[3] = {pp[0] - cp[0], pp[1] - cp[1], pp[2] - cp[2]};
@@ -1641,7 +1639,7 @@ struct TPhys {
       const float dist = unique ? -sp : 1.0f;
       for (int q = 0; q < 3; q++) pos[q] = vw[q] - 0.5f * dist * nw[q];
       make_frame(fr, nw);
-      P1::store_contact(Ls, 4 * p + sub, dist, pos, fr);
+      Ph::store_contact(L, 4 * p + sub, dist, pos, fr);
     }
   }
 
@@ -2096,8 +2094,7 @@ struct TPhys {
     const int p = Md::PLANE_PAIR[0] * (1 - h) + Md::PLANE_PAIR[1] * h;
     const int gs = cgeom_slot<Md>(Md::pair_geom2[p]);
     float pp[3], PR[9], cp[3], CR[9];
-    S1 Ls{L};
-    P1::geom_frame(Ls, 0, pp, PR);
+    Ph::geom_frame(L, 0, pp, PR);
     cgeom_frame(L, gs, cp, CR);
     float R[9], t[3];  // mesh -> local rotation; the hull frame's origin in the field frame
     for (int a = 0; a < 3; a++)
@@ -2531,11 +2528,11 @@ struct TPhys {
         for (int a = 0; a < 3; a++) pw[a] += pp[a];
         mulmv3(nw, PR, pn);
         make_frame(fr, nw);
-        P1::store_contact(Ls, 4 * p + sub, unique ? -pd : 1.0f, pw, fr);
+        Ph::store_contact(L, 4 * p + sub, unique ? -pd : 1.0f, pw, fr);
       } else {
         const float nofr[9] = {0, 0, 1, 0, 1, 0, -1, 0, 0};
         const float zero[3] = {L[Ly::COM], L[Ly::COM + 1], L[Ly::COM + 2]};
-        P1::store_contact(Ls, 4 * p + sub, 1.0f, zero, nofr);
+        Ph::store_contact(L, 4 * p + sub, 1.0f, zero, nofr);
       }
     }
 #if defined(DUCK_DOUBLE) && DUCK_DOUBLE == 19
@@ -2586,7 +2583,7 @@ struct TPhys {
   // axes split over the lanes, then mjx's clipped face manifold or the edge pair's closest points. Face axes (both hulls, 60) then edge-pair axes (45 x 45); a
   // separating axis anywhere means no contact (the 4 slots stay inactive); otherwise the best
   // face (largest separation, first index among equal ones) unless the best edge pair beats it
-  // by 1e-9 (declared deviation: the single-lane scan applies that margin per step, here it is
+  // by 1e-9 (declared deviation: a sequential scan applies that margin per step, here it is
   // applied to the edges' maximum). Vertices and edge directions in world coordinates are kept
   // in registers (vertices) and in the dead H / constraint-row storage (edges).
   static DK void collide_hulls_team(LP L, int lane, int slot0, const float* p1, const float* R1, const float* p2,
@@ -2594,11 +2591,10 @@ struct TPhys {
     constexpr int NH = Md::NHV, NF = Md::NHF, NE = Md::NHE;
     constexpr int EA = Ly::H, EB = EA + 3 * NE;
     static_assert(EB + 3 * NE <= Ly::CR, "edge scratch must fit in the H / row storage");
-    S1 Ls{L};
     if (lane < 4) {
       const float nofr[9] = {0, 0, 1, 0, 1, 0, -1, 0, 0};
       const float zero[3] = {L[Ly::COM], L[Ly::COM + 1], L[Ly::COM + 2]};
-      P1::store_contact(Ls, slot0 + lane, 1.0f, zero, nofr);
+      Ph::store_contact(L, slot0 + lane, 1.0f, zero, nofr);
     }
     float V1[NH][3], V2[NH][3], t[3];
 #pragma unroll
@@ -2737,7 +2733,7 @@ struct TPhys {
       bj = ebest - bi * NE;
       for (int q = 0; q < 3; q++) u_best[q] = u_edge[q];
     }
-    // the contact, uniform over the team (the single-lane code's tail)
+    // the contact, uniform over the team
     TSYNC();
     float fr[9];
     make_frame(fr, u_best);
@@ -2759,7 +2755,7 @@ struct TPhys {
       sc = fminf(fmaxf(sc, 0.0f), 1.0f);
       float pos[3];
       for (int a = 0; a < 3; a++) pos[a] = 0.5f * (a0[a] + sc * d1[a] + b0[a] + tt * d2[a]);
-      if (lane == 0) P1::store_contact(Ls, slot0, best, pos, fr);
+      if (lane == 0) Ph::store_contact(L, slot0, best, pos, fr);
       return;
     }
     // face contact, mjx's clipped manifold (oracle collide_convex_convex): the incident face (the
@@ -2852,7 +2848,7 @@ struct TPhys {
       float v[3], pos[3];
       pick3<CLIPMAX>(poly, idx[c], v);
       for (int a = 0; a < 3; a++) pos[a] = v[a] - 0.5f * dist * fn[a];
-      P1::store_contact(Ls, slot0 + c, dist, pos, fr);
+      Ph::store_contact(L, slot0 + c, dist, pos, fr);
     }
   }
 
@@ -2861,10 +2857,9 @@ struct TPhys {
   static DNI void collide_hulls_rare(LP L, int lane) {
     constexpr int p = Md::FOOT_PAIR < 0 ? 0 : Md::FOOT_PAIR;
     const int s1 = cgeom_slot<Md>(Md::pair_geom1[p]), s2 = cgeom_slot<Md>(Md::pair_geom2[p]);
-    S1 Ls{L};
     float p1[3], R1[9], p2[3], R2[9], t[3], c1[3], c2[3];
-    P1::geom_frame(Ls, s1, p1, R1);
-    P1::geom_frame(Ls, s2, p2, R2);
+    Ph::geom_frame(L, s1, p1, R1);
+    Ph::geom_frame(L, s2, p2, R2);
     const float hc[3] = {Md::hull_center[0], Md::hull_center[1], Md::hull_center[2]};
     mulmv3(t, R1, hc);
     for (int a = 0; a < 3; a++) c1[a] = p1[a] + t[a];
@@ -2882,11 +2877,10 @@ struct TPhys {
     if (Md::FOOT_PAIR >= 0) {
       constexpr int p = Md::FOOT_PAIR;
       const int s1 = cgeom_slot<Md>(Md::pair_geom1[p]), s2 = cgeom_slot<Md>(Md::pair_geom2[p]);
-      S1 Ls{L};
       // bounding-sphere reject (the common case) is uniform over the team
       float p1[3], R1[9], p2[3], R2[9], t[3];
-      P1::geom_frame(Ls, s1, p1, R1);
-      P1::geom_frame(Ls, s2, p2, R2);
+      Ph::geom_frame(L, s1, p1, R1);
+      Ph::geom_frame(L, s2, p2, R2);
       float c1[3], c2[3];
       const float hc[3] = {Md::hull_center[0], Md::hull_center[1], Md::hull_center[2]};
       mulmv3(t, R1, hc);
@@ -2898,7 +2892,7 @@ struct TPhys {
         if (lane < 4) {
           const float nofr[9] = {0, 0, 1, 0, 1, 0, -1, 0, 0};
           const float zero[3] = {L[Ly::COM], L[Ly::COM + 1], L[Ly::COM + 2]};
-          P1::store_contact(Ls, 4 * p + lane, 1.0f, zero, nofr);
+          Ph::store_contact(L, 4 * p + lane, 1.0f, zero, nofr);
         }
       } else {
         TSYNC();
@@ -2969,8 +2963,8 @@ struct TPhys {
     const float mu = tf(o + 2);
     const float r[3] = {L[Ly::CR + 3 * slot], L[Ly::CR + 3 * slot + 1], L[Ly::CR + 3 * slot + 2]};
     float v[3] = {0.0f, 0.0f, 0.0f}, t[3];
-    if (s2 != 0) { P1::contact_vel(s2 == 1 ? SL : SR, r, t); v[0] += t[0]; v[1] += t[1]; v[2] += t[2]; }
-    if (s1 != 0) { P1::contact_vel(s1 == 1 ? SL : SR, r, t); v[0] -= t[0]; v[1] -= t[1]; v[2] -= t[2]; }
+    if (s2 != 0) { Ph::contact_vel(s2 == 1 ? SL : SR, r, t); v[0] += t[0]; v[1] += t[1]; v[2] += t[2]; }
+    if (s1 != 0) { Ph::contact_vel(s1 == 1 ? SL : SR, r, t); v[0] -= t[0]; v[1] -= t[1]; v[2] -= t[2]; }
     float jr[3];
     for (int q = 0; q < 3; q++)
       jr[q] = L[Ly::CFR + 9 * slot + 3 * q] * v[0] + L[Ly::CFR + 9 * slot + 3 * q + 1] * v[1] +
@@ -3636,8 +3630,7 @@ struct TPhys {
     if (want_out) {
       sensors(L, lane);
       if (aux) {
-        S1 Ls{L};
-        if (lane == 0) P1::write_aux(Ls, aux, aux_stride);
+        if (lane == 0) Ph::write_aux(L, aux, aux_stride);
       }
     }
     if (integrate) {

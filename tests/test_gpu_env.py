@@ -84,16 +84,47 @@ def test_autoreset_and_episode(gpu):
     env = wrap_for_brax_training(Joystick("flat_terrain", num_envs=n, device=gpu, use_imitation=False),
                                  episode_length=5)
     st = env.reset(rng=3)
-    first_obs = st.obs["state"].clone()
+    first = {key: st.obs[key].clone() for key in ("state", "privileged_state")}
     for t in range(5):
         st = env.step(st, torch.zeros(n, env.action_size, device=gpu))
     torch.cuda.synchronize()
-    # episode_length reached: every env is done and restored to its first state
+    # episode_length reached: every env is done and restored to its first state (both rows, bit for bit)
     assert torch.all(st.done == 1)
-    assert torch.allclose(st.obs["state"], first_obs)
+    for key in first:
+        assert torch.equal(st.obs[key], first[key]), key
     assert torch.all(st.info["steps"] == 5)
     st = env.step(st, torch.zeros(n, env.action_size, device=gpu))
     assert torch.all(st.info["steps"] == 1)
+
+
+def test_masked_reset(gpu):
+    """reset(mask=...) rewrites the masked envs' state columns and rows exactly as a fresh reset does
+    (reset is keyed by seed and global env id) and leaves every other env's bits alone. 37 envs: two
+    full workgroups and a partial one; the mask takes env 0, env 36 and two envs of one wave (8, 9)."""
+    n = 37
+    env = Joystick("flat_terrain", num_envs=n, device=gpu, use_imitation=True)
+    rng = np.random.default_rng(2)
+    st = env.reset(rng=5)
+    for _ in range(2):
+        a = rng.uniform(-1, 1, (n, env.action_size)).astype(np.float32)
+        st = env.step(st, torch.tensor(a, device=gpu), inplace=True)
+
+    def snap(s):
+        return {"fstate": s.fstate.view(-1, n).t().clone(), "istate": s.istate.view(-1, n).t().clone(),
+                "obs": s.obs["state"].clone(), "priv": s.obs["privileged_state"].clone()}
+
+    before = snap(st)
+    m = torch.zeros(n, dtype=torch.bool)
+    m[[0, 2, 5, 8, 9, 12, 15, 16, 19, 21, 22, 25, 27, 30, 31, 33, 35, 36]] = True
+    st = env.reset(rng=5, mask=m, state=st)
+    after = snap(st)
+    fresh = snap(Joystick("flat_terrain", num_envs=n, device=gpu, use_imitation=True).reset(rng=5))
+    torch.cuda.synchronize()
+    m = m.to(gpu)
+    for key in before:
+        assert not torch.equal(before[key][m], fresh[key][m]), key  # (the two steps did change them)
+        assert torch.equal(after[key][~m], before[key][~m]), key
+        assert torch.equal(after[key][m], fresh[key][m]), key
 
 
 @pytest.mark.parametrize("task", ["flat_terrain", "rough_terrain", "rough_terrain_backlash"])
