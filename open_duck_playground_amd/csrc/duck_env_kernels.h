@@ -55,10 +55,12 @@ DK int local_env(int& lane) {
   return threadIdx.x / TEAM;
 }
 
-// env t's slice of the workgroup's LDS (contiguous: element k at L[k])
+// env t's slice of the workgroup's LDS (contiguous: element k at L[k]); 16-byte aligned (the dynamic
+// LDS is, and STRIDE % 4 == 0: duck_physics.h LDS_ALIGNED)
 template <class Md, int LAT = 0>
 DK lds_float* env_slice(float* lds, int t) {
-  return (lds_float*)(lds + t * TLay<Md, LAT>::STRIDE);
+  static_assert(TLay<Md, LAT>::STRIDE % 4 == 0, "an env slice starts 16-byte aligned");
+  return lds_assume16((lds_float*)(lds + t * TLay<Md, LAT>::STRIDE));
 }
 
 // one substep (TPhys::step). The forwarding layer is kept: with step called directly the height-field
@@ -277,7 +279,7 @@ template <class Md>
 __global__ void __launch_bounds__(TPB) reset_kernel(KArgs A) {
   using Ly = Lay<Md>;
   {
-    extern __shared__ float lds_t[];
+    extern __shared__ LDS_ALIGNED float lds_t[];
     load_model_tables<Md>(lds_t);
   }
   int lane;
@@ -285,7 +287,7 @@ __global__ void __launch_bounds__(TPB) reset_kernel(KArgs A) {
   const int e = blockIdx.x * TEAM_WG + t;
   if (e >= A.n) return;
   if (A.mask && !A.mask[e]) return;
-  extern __shared__ float lds[];
+  extern __shared__ LDS_ALIGNED float lds[];
   lds_float* const L = env_slice<Md>(lds, t);
   const duck_env_config& c = A.cfg;
   const duck_layout& Lo = A.lay;
@@ -687,7 +689,7 @@ __global__ void __launch_bounds__(TPB) step_kernel(KArgs A) {
 #endif
   using TL = TLay<Md>;
   {
-    extern __shared__ float lds_t[];
+    extern __shared__ LDS_ALIGNED float lds_t[];
     load_model_tables<Md>(lds_t);
   }
   STAGE_MARK(14);
@@ -695,7 +697,7 @@ __global__ void __launch_bounds__(TPB) step_kernel(KArgs A) {
   const int t = local_env(lane);
   const int e = blockIdx.x * TEAM_WG + t;
   const int n = A.n;
-  extern __shared__ float lds[];
+  extern __shared__ LDS_ALIGNED float lds[];
   if constexpr (TL::ES_LDS) {
     // hot state <-> LDS by the whole workgroup, field-major: a wave instruction moves 4 fields
     // x 16 consecutive envs (four 64-B segments of the [field][env] rows) instead of 16 fields x
@@ -788,7 +790,7 @@ __device__ __forceinline__ void step_lat_body(KArgs A) {
   static_assert(TL::TAB_LDS && TL::ES_LDS, "latency mode: the model blob and the hot state in LDS");
   static_assert(TPB == 4 * 64 && WGL * TEAM == 64 * (LAT == 2 ? 2 : 1),
                 "latency modes: 4 waves, one set of 4 teams per wave (paired: per pair of waves)");
-  extern __shared__ float lds[];
+  extern __shared__ LDS_ALIGNED float lds[];
   LAT_T(40, 5);
   TPL::ev_init((int)threadIdx.x);
   load_model_tables<Md, LAT>(lds);  // (ends with a workgroup barrier: the event counters are 0 before any wait)
@@ -908,7 +910,7 @@ __global__ void __launch_bounds__(TPB) physics_kernel(KArgs A, float* qpos_g, fl
                                                      const float* ctrl_g, int nsub, float* aux) {
   using Ly = Lay<Md>;
   {
-    extern __shared__ float lds_t[];
+    extern __shared__ LDS_ALIGNED float lds_t[];
     load_model_tables<Md>(lds_t);
   }
   int lane;
@@ -916,7 +918,7 @@ __global__ void __launch_bounds__(TPB) physics_kernel(KArgs A, float* qpos_g, fl
   const int e = blockIdx.x * TEAM_WG + t;
   const int n = A.n;
   if (e >= n) return;
-  extern __shared__ float lds[];
+  extern __shared__ LDS_ALIGNED float lds[];
   lds_float* const L = env_slice<Md>(lds, t);
   for (int i = 0; i < Md::NQ; i++) L[Ly::QPOS + i] = qpos_g[(size_t)i * n + e];
   for (int i = 0; i < Md::NV; i++) { L[Ly::QVEL + i] = qvel_g[(size_t)i * n + e]; L[Ly::WARM + i] = warm_g[(size_t)i * n + e]; }
@@ -1109,7 +1111,32 @@ static int stage_cycles_of(unsigned long long* out, int reset) {
 }
 
 // one VariantOps table per compiled model (a host function, so the device pass skips it)
+// What each shipped scene keeps in LDS, pinned: a layout change (padding, record strides) that pushed
+// the model blob or the staged hot state out to global memory, or cost a latency split, would still
+// compile and run, only slower. Every scene: the model blob, both latency splits; flat and rough: the
+// hot state too; flat: the two-workgroups-per-CU latency kernel. Other models (native.model_library)
+// take what fits.
+constexpr bool name_is(const char* a, const char* b) {
+  for (; *a && *a == *b; a++, b++) {}
+  return *a == *b;
+}
+template <class Md>
+constexpr bool lds_budget_kept(const char* name) {
+  const bool flat = name_is(name, "flat"), rough = name_is(name, "rough");
+  if (!flat && !rough && !name_is(name, "backlash") && !name_is(name, "rough_backlash")) return true;
+  return TLay<Md>::TAB_LDS && TLay<Md, 1>::FITS && TLay<Md, 2>::FITS && (!(flat || rough) || TLay<Md>::ES_LDS) &&
+         (!flat || LatX2<Md>::PAYS);
+}
+template <class Md>
+constexpr bool slices_aligned() {
+  return TLay<Md>::STRIDE % 4 == 0 && TLay<Md>::TAB % 4 == 0 && TLay<Md, 1>::STRIDE % 4 == 0 && TLay<Md, 1>::TAB % 4 == 0 &&
+         TLay<Md, 2>::STRIDE % 4 == 0 && TLay<Md, 2>::TAB % 4 == 0 && TLay<Md, LAT_X2>::STRIDE % 4 == 0 &&
+         TLay<Md, LAT_X2>::TAB % 4 == 0;
+}
+
 #define DUCK_DEFINE_VARIANT(NAME, MODEL)                                                        \
+  static_assert(lds_budget_kept<MODEL>(#NAME), "scene " #NAME " no longer keeps in LDS what it kept"); \
+  static_assert(slices_aligned<MODEL>(), "16-byte env slices and model blob in every step mode");  \
   const VariantOps* duck_variant_##NAME() {                                                     \
     static const VariantOps ops = {#NAME,               matches<MODEL>,         aux_size_of<MODEL>, \
                                    lds_bytes<MODEL>,    MODEL::FLOOR_TYPE,      launch_reset<MODEL>, \

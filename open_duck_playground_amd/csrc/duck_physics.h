@@ -22,6 +22,18 @@
 // passed into a non-inlined stage would compile to flat_load/flat_store through the
 // vector-memory pipe)
 typedef __attribute__((address_space(3))) float lds_float;
+// The alignment contract of the dynamic LDS: every declaration of it is 16-byte aligned, every env
+// slice starts a multiple of 4 floats into it (TLay: STRIDE % 4 == 0), and env_slice() says so, so a
+// run of 2 / 4 words that starts at an even / 4-aligned Lay offset is one ds_read_b64 / _b128 with a
+// 16-bit byte offset instead of ds_read2_b32s behind a v_add_u32 (their offsets reach 1020 B only).
+// A wide access off its alignment does not fault, it replays (SQ_LDS_UNALIGNED_STALL): a pointer
+// that is not a slice base + a compile-time offset must not carry the assumption (the staged hot
+// state, ESTRIDE odd).
+#define LDS_ALIGNED __attribute__((aligned(16)))
+DK lds_float* lds_assume16(lds_float* p) {
+  __builtin_assume(((unsigned)(__SIZE_TYPE__)p & 15u) == 0u);
+  return p;
+}
 
 // optional per-stage cycle counters (build with -DDUCK_STAGE_PROF; read by duck_debug_stage_cycles);
 // -DDUCK_WAVE_PROF records only the per-wave launch cycles (no stage marks perturbing wave 0)
@@ -90,27 +102,74 @@ static __device__ unsigned long long g_stage_wg[DUCK_NSTAGE * 256];
 // the state row is its prefix (write_obs_team, duck_env_kernels.h)
 constexpr int priv_row_max(int nu) { return DUCK_OBS_SIZE(nu) + 15 + 3 * nu + 1 + 2 + 6 + 2 + 40 + 1 + 2; }
 
-// Per-env LDS slice layout (floats); a slice is contiguous and addressed through an lds_float*
+// What a workgroup's 160 KB of LDS holds next to the throughput kernel's 16 env slices decides how much
+// padding a slice may carry: lay_keeps() says, for slices of `total` words, whether the model blob
+// (bit 0), else the hull SAT tables (bit 1), and the staged hot state (bit 2) stay in LDS, or -1 when
+// the slices alone do not fit. The same sums as TLay<Md, 0> (duck_team.h), which asserts that they agree.
+constexpr int LDS_WORDS = 160 * 1024 / 4;
+constexpr int SLICES_WG = 16;  // env slices per throughput workgroup (= TEAM_WG)
+// per-lane dump slots after the Lay fields (TLay::SINK, 2 x TEAM words; debug line-search dumps use 136)
+#ifdef DUCK_LS_DUMP
+constexpr int SINK_WORDS = 136;
+#else
+constexpr int SINK_WORDS = 32;
+#endif
+constexpr int slice_stride(int used) { return ((used + 15) / 32) * 32 + 16; }  // = 16 (mod 32), >= used
+// step_kernel's staged hot state (the duck_layout fields before first_qpos) + the step's 64 random draws
 template <class Md>
-struct Lay {
+constexpr int hot_words() { return Md::NQ + 2 * Md::NV + 8 * Md::NU + 77; }
+constexpr int hot_stride(int hot) { return (hot + 64) | 1; }  // odd: distinct banks
+template <class Md>
+constexpr int lay_keeps(int total) {
+  const int tab = SLICES_WG * slice_stride(total + SINK_WORDS);
+  const int nht = Md::B_HEND > Md::B_HFACE ? Md::B_HEND - Md::B_HFACE : 0;
+  const bool tabl = tab + Md::NBLOB <= LDS_WORDS, htl = !tabl && nht > 0 && tab + nht <= LDS_WORDS;
+  const int es = tab + (tabl ? Md::NBLOB : (htl ? nht : 0));
+  const bool esl = es + SLICES_WG * hot_stride(hot_words<Md>()) <= LDS_WORDS;
+  return es > LDS_WORDS ? -1 : tabl + 2 * htl + 4 * esl;
+}
+
+// Per-env LDS slice layout (floats); a slice is contiguous and addressed through an lds_float*.
+//
+// Order and padding serve the alignment contract (LDS_ALIGNED above): the fields whose records a lane
+// reads or writes whole -- poses, frames, inertias, 6-vectors, the tree passes' scratch, the constraint
+// rows' records -- come first and start on 4-float boundaries, the lane-indexed vectors (state,
+// per-env model values), which gain nothing from alignment, come last. Most boundaries fall out of
+// the sizes (4 NB, 10 NB, 6 NB, 6 NV, 18 + NM + 1 with NM odd ...); where one does not, a4() / a2()
+// pad up to AL floats. A scene gets the even record strides (WIDE) and AL = 4 where such slices leave
+// in LDS what packed ones do (lay_keeps), else what of it fits (lay_rule): rough + backlash has 9 words
+// a slice to spare, and the same order without padding still puts most records on their boundaries.
+// (-DDUCK_LAY_WIDE=0: every scene with the odd record strides, for A/B builds)
+#ifndef DUCK_LAY_WIDE
+#define DUCK_LAY_WIDE 1
+#endif
+template <class Md, int AL, bool WIDE>
+struct LayT {
+  static constexpr int ALIGN = AL, WIDE_RECORDS = WIDE;
   static constexpr int NB = Md::NB, NV = Md::NV, NQ = Md::NQ, NU = Md::NU;
   static constexpr int NCON = 4 * Md::NPAIR;
   static constexpr int R_LIM = Md::NFRIC, R_CON = Md::NFRIC + Md::NLIM;
   static constexpr int NROW = R_CON + 4 * NCON;
-  // state
-  static constexpr int QPOS = 0, QVEL = QPOS + NQ, WARM = QVEL + NV, CTRL = WARM + NV, QACC = CTRL + NU;
-  static constexpr int QSM = QACC + NV, FSM = QSM + NV, SRCH = FSM + NV, GRAD = SRCH + NV, MA = GRAD + NV;
-  // per-env model values (domain randomisation)
-  static constexpr int DMASS = MA + NV, DIPOS = DMASS + NB, DARM = DIPOS + 3, DFRIC = DARM + NV;
-  static constexpr int DQ0 = DFRIC + NV, DKP = DQ0 + NQ;
+  static constexpr int up(int x, int a) { return (x + a - 1) / a * a; }
+  static constexpr int a4(int x) { return up(x, AL < 4 ? AL : 4); }  // 16-byte fields
+  static constexpr int a2(int x) { return up(x, AL < 2 ? AL : 2); }  // 8-byte fields
+  // a per-row array whose contact rows (4 per contact, from R_CON on) start on a 4-float boundary
+  static constexpr int arow(int x) { return a4(x + R_CON) - R_CON; }
+  // record strides of the fields indexed per lane (words per body / per contact slot): body positions,
+  // body frames, contact points, contact frames. WIDE: even, so that a lane's record is ds_read_b64 /
+  // _b128s (3 -> 4 and 9 -> 10 words: 60 more words a slice); else packed and odd (conflict-free banks
+  // over the lanes of a team, b32 accesses only). DESIGN.md §3 has the counts and the measurements.
+  static constexpr int XPS = WIDE ? 4 : 3, XMS = WIDE ? 10 : 9, CRS = WIDE ? 4 : 3, CFS = WIDE ? 10 : 9;
   // bodies
-  static constexpr int XPOS = DKP + NU, XQ = XPOS + 3 * NB, XMAT = XQ + 4 * NB, CIN = XMAT + 9 * NB;
-  static constexpr int CVEL = CIN + 10 * NB, COM = CVEL + 6 * NB;
-  static constexpr int CDOF = COM + 3, CDD1 = CDOF + 6 * NV;
+  static constexpr int XQ = 0, XMAT = XQ + 4 * NB, XPOS = a4(XMAT + XMS * NB), CIN = a4(XPOS + XPS * NB);
+  static constexpr int CVEL = a4(CIN + 10 * NB), CDOF = a4(CVEL + 6 * NB);
   // matrices
   // M, then one word kept at zero (crb writes it with M): the register column
   // loads of M read it for the entries outside the tree pattern (codegen mcolz table)
-  static constexpr int M = CDD1 + 18, MZERO = M + Md::NM, H = MZERO + 1;
+  static constexpr int M = a4(CDOF + 6 * NV), MZERO = M + Md::NM, CDD1 = a2(MZERO + 1);
+  // the subtree centre of mass, then the small outputs of the last forward (3 + 3 + 2 + 2 + 2 words)
+  static constexpr int COM = a4(CDD1 + 18), IMUR = COM + 3, OCON = IMUR + 3, FOOTZ = OCON + 2, FLAGS = FOOTZ + 2;
+  static constexpr int H = a4(FLAGS + 2);
   // H: scratch in front of the constraint rows, dead outside the stage that uses it together with
   // the rows (the Newton Hessian itself is assembled in registers, never stored). Its users, each
   // from H on: the tree passes' scratch (rne: 12 NB + 6 NV), the hull/hull SAT's edge tables (6 per
@@ -123,17 +182,47 @@ struct Lay {
   static constexpr int cmax(int a, int b) { return a > b ? a : b; }
   static constexpr int SCR_NEED = cmax(cmax(SCR_TREE, SCR_SAT), cmax(SCR_HF, SCR_OBS));
   static constexpr int HSZ = ((cmax(SCR_NEED - 4 * NROW - Md::NLIM, 0) + 3) / 4) * 4;
-  static constexpr int JA = H + HSZ, JV = JA + NROW, RD = JV + NROW, AREF = RD + NROW;
-  static constexpr int LSGN = AREF + NROW;
-  static constexpr int CR = LSGN + Md::NLIM, CFR = CR + 3 * NCON, CDIST = CFR + 9 * NCON;
+  static constexpr int JA = arow(H + HSZ), JV = arow(JA + NROW), RD = arow(JV + NROW), AREF = arow(RD + NROW);
+  static constexpr int LSGN = a2(AREF + NROW);
+  static constexpr int CR = a4(LSGN + Md::NLIM), CFR = a4(CR + CRS * NCON), CDIST = a4(CFR + CFS * NCON);
+  static_assert(CR - H >= SCR_NEED, "H + rows must cover the scratch users");
   // Newton 6x6 foot blocks live in CIN's storage (composite inertias are dead after crb())
-  static constexpr int KL = CIN, KR = KL + 21, KLR = KR + 21, FL = KLR + 36, FR = FL + 6;
+  static constexpr int KL = CIN, KR = a2(KL + 21), KLR = a2(KR + 21), FL = KLR + 36, FR = FL + 6;
   static_assert(FR + 6 <= CIN + 10 * NB, "Newton blocks must fit in CIN");
-  // outputs of the last forward
-  static constexpr int AF = CDIST + NCON, SENS = AF + NU, OCON = SENS + Md::NSENSORDATA, IMUR = OCON + 2,
-                       FOOTZ = IMUR + 3, FLAGS = FOOTZ + 2;
-  static constexpr int TOTAL = FLAGS + 2;
+  // larger outputs of the last forward
+  static constexpr int AF = a2(CDIST + NCON), SENS = a2(AF + NU);
+  // state
+  static constexpr int QPOS = SENS + Md::NSENSORDATA, QVEL = QPOS + NQ, WARM = QVEL + NV, CTRL = WARM + NV;
+  static constexpr int QACC = CTRL + NU;
+  static constexpr int QSM = QACC + NV, FSM = QSM + NV, SRCH = FSM + NV, GRAD = SRCH + NV, MA = GRAD + NV;
+  // per-env model values (domain randomisation), contiguous in the order of the model blob's nominal block
+  static constexpr int DMASS = MA + NV, DIPOS = DMASS + NB, DARM = DIPOS + 3, DFRIC = DARM + NV;
+  static constexpr int DQ0 = DFRIC + NV, DKP = DQ0 + NQ;
+  static constexpr int TOTAL = a4(DKP + NU);
+  // what the layout promises the compiler's alignment analysis (each holds for AL = 4)
+  static_assert(AL < 4 || (XQ % 4 == 0 && XMAT % 4 == 0 && CIN % 4 == 0 && CVEL % 4 == 0 && CDOF % 4 == 0 && M % 4 == 0 &&
+                           COM % 4 == 0 && H % 4 == 0 && (JA + R_CON) % 4 == 0 && (JV + R_CON) % 4 == 0 &&
+                           (RD + R_CON) % 4 == 0 && (AREF + R_CON) % 4 == 0 && CR % 4 == 0 && CFR % 4 == 0 &&
+                           CDIST % 4 == 0 && TOTAL % 4 == 0),
+                "16-byte fields");
+  static_assert(AL < 2 || (XPOS % 2 == 0 && CDD1 % 2 == 0 && KR % 2 == 0 && KLR % 2 == 0 && FL % 2 == 0 && FR % 2 == 0 &&
+                           LSGN % 2 == 0 && AF % 2 == 0 && SENS % 2 == 0),
+                "8-byte fields");
 };
+// the layout rule a scene affords: the first of (WIDE, AL) = (1, 4), (1, 2), (1, 1), (0, 4), (0, 2), (0, 1)
+// whose slices keep in LDS what the packed slices (0, 1) keep; returned as 8 WIDE + AL
+template <class Md>
+constexpr int lay_rule() {
+  constexpr int keep = lay_keeps<Md>(LayT<Md, 1, false>::TOTAL);
+  if (DUCK_LAY_WIDE) {
+    if (lay_keeps<Md>(LayT<Md, 4, true>::TOTAL) == keep) return 8 + 4;
+    if (lay_keeps<Md>(LayT<Md, 2, true>::TOTAL) == keep) return 8 + 2;
+    if (lay_keeps<Md>(LayT<Md, 1, true>::TOTAL) == keep) return 8 + 1;
+  }
+  return lay_keeps<Md>(LayT<Md, 4, false>::TOTAL) == keep ? 4 : (lay_keeps<Md>(LayT<Md, 2, false>::TOTAL) == keep ? 2 : 1);
+}
+template <class Md>
+struct Lay : LayT<Md, lay_rule<Md>() & 7, (lay_rule<Md>() >> 3) != 0> {};
 
 // solref/solimp -> (k, b, imp) (mjx constraint._kbi / MuJoCo mj_makeImpedance)
 DK void kbi(const float* solref, const float* solimp, float pos, float dt, float& k, float& b, float& imp) {
@@ -295,10 +384,10 @@ struct Phys {
     } else {
       float R[9], t[3];
 #pragma unroll
-      for (int k = 0; k < 9; k++) R[k] = L[Ly::XMAT + 9 * b + k];
+      for (int k = 0; k < 9; k++) R[k] = L[Ly::XMAT + Ly::XMS * b + k];
       mulmv3(t, R, Md::geom_pos[g]);
 #pragma unroll
-      for (int k = 0; k < 3; k++) gp[k] = L[Ly::XPOS + 3 * b + k] + t[k];
+      for (int k = 0; k < 3; k++) gp[k] = L[Ly::XPOS + Ly::XPS * b + k] + t[k];
       mulmm3(gR, R, Md::geom_mat[g]);
     }
   }
@@ -306,9 +395,9 @@ struct Phys {
   static DK void store_contact(lds_float* L, int slot, float dist, const float* pos, const float* fr) {
     L[Ly::CDIST + slot] = dist;
 #pragma unroll
-    for (int a = 0; a < 3; a++) L[Ly::CR + 3 * slot + a] = pos[a] - L[Ly::COM + a];
+    for (int a = 0; a < 3; a++) L[Ly::CR + Ly::CRS * slot + a] = pos[a] - L[Ly::COM + a];
 #pragma unroll
-    for (int a = 0; a < 9; a++) L[Ly::CFR + 9 * slot + a] = fr[a];
+    for (int a = 0; a < 9; a++) L[Ly::CFR + Ly::CFS * slot + a] = fr[a];
   }
 
   // ---------------- constraint rows (mjx make_constraint) ----------------
@@ -330,13 +419,13 @@ struct Phys {
     for (int k = 0; k < Md::NSENSORDATA; k++) aux[(o++) * stride] = L[Ly::SENS + k];
     for (int s = 0; s < NCON; s++) aux[(o++) * stride] = L[Ly::CDIST + s];
     for (int s = 0; s < NCON; s++)
-      for (int a = 0; a < 3; a++) aux[(o++) * stride] = L[Ly::CR + 3 * s + a] + L[Ly::COM + a];
+      for (int a = 0; a < 3; a++) aux[(o++) * stride] = L[Ly::CR + Ly::CRS * s + a] + L[Ly::COM + a];
     for (int s = 0; s < NCON; s++)
-      for (int a = 0; a < 3; a++) aux[(o++) * stride] = L[Ly::CFR + 9 * s + a];  // contact normal
+      for (int a = 0; a < 3; a++) aux[(o++) * stride] = L[Ly::CFR + Ly::CFS * s + a];  // contact normal
     for (int k = 0; k < Md::NM; k++) aux[(o++) * stride] = L[Ly::M + k];
 #ifdef DUCK_AUX_LDS
-    // debug builds: the whole env slice (Lay fields + the team's chain/spatial scratch)
-    for (int k = 0; k < Ly::TOTAL + 12 * Md::MAXCHAIN + 24; k++) aux[(o++) * stride] = L[k];
+    // debug builds: the whole env slice (Lay fields + the per-lane dump slots; tools/diag_lds.py)
+    for (int k = 0; k < Ly::TOTAL + SINK_WORDS; k++) aux[(o++) * stride] = L[k];
 #endif
   }
 };
@@ -345,7 +434,7 @@ template <class Md>
 constexpr int aux_size() {
   return 4 * Md::NV + Md::NU + Md::NSENSORDATA + 7 * Lay<Md>::NCON + Md::NM
 #ifdef DUCK_AUX_LDS
-         + Lay<Md>::TOTAL + 12 * Md::MAXCHAIN + 24
+         + Lay<Md>::TOTAL + SINK_WORDS
 #endif
       ;
 }

@@ -283,11 +283,8 @@ struct TLay {
   using Ly = Lay<Md>;
   // per-lane dump slots (SINK, 2 x TEAM words; debug line-search dumps use 136 words from here)
   static constexpr int KC = Ly::TOTAL;
-#ifdef DUCK_LS_DUMP
-  static constexpr int USED0 = KC + 136;
-#else
-  static constexpr int USED0 = KC + 2 * TEAM;
-#endif
+  static constexpr int USED0 = KC + SINK_WORDS;
+  static_assert(SINK_WORDS >= 2 * TEAM && SLICES_WG == TEAM_WG, "duck_physics.h lay_keeps");
   // the height field's per-foot silhouette lists (collide_hfield -> hf_exec)
   static constexpr int HF_SLF = (1 + Md::HF_SILCAP + 3) & ~3;
   static constexpr int HF_SLSZ = HF_SLF + 4 * Md::HF_SILCAP;
@@ -303,9 +300,14 @@ struct TLay {
   // the speculative Newton direction of wave 3 (latency mode): NV floats, then the team's valid flag
   static constexpr int XDIR = LAT ? ((XSIL + (Md::FLOOR_TYPE == 1 ? 2 * HF_SLSZ : 0) + 3) & ~3) : 0;
   static constexpr int USED = LAT ? XDIR + Md::NV + 4 : USED0;
-  static constexpr int STRIDE = ((USED + 15) / 32) * 32 + 16;  // = 16 (mod 32), >= USED
+  static constexpr int STRIDE = slice_stride(USED);  // = 16 (mod 32), >= USED
   static constexpr int NWG = LAT == 2 ? 2 * LAT_WG : (LAT ? LAT_WG : TEAM_WG);  // envs per workgroup
   static_assert(STRIDE >= USED && STRIDE % 32 == 16, "stride");
+  // the alignment contract (duck_physics.h LDS_ALIGNED): slices and what follows them start 16-byte
+  // aligned, and so do the regions a latency slice adds behind the throughput slice's words
+  static_assert(STRIDE % 4 == 0 && (STRIDE * NWG) % 4 == 0, "16-byte slices");
+  static_assert(XRNE % (Ly::ALIGN < 4 ? Ly::ALIGN : 4) == 0 && (!LAT || (XRNE % 4 == 0 && XCIN % 4 == 0 && XDUM0 % 2 == 0 &&
+                XDUM1 % 2 == 0 && XSIL % 4 == 0 && XDIR % 4 == 0)), "16-byte scratch regions");
   // per-lane dump slots for branchless conditional stores (L[ok ? addr : SINK + lane] = v): a
   // lane-divergent `if` leaves a join block whose exec restore the register allocator may put
   // live-range split copies in front of (tools/isa_exec_check.py), so the hot
@@ -314,15 +316,18 @@ struct TLay {
   // scratch of the flattened tree passes: the H + constraint-row storage is dead until the
   // constraint stage (kinematics / rne / crb run before it)
   static constexpr int TMP = Ly::H;
-  static constexpr int KLOC = TMP;                               // local body transforms (7 per body)
-  static_assert(7 * Md::NB <= Ly::HSZ + 4 * Ly::NROW, "tree scratch must fit in H + rows");
+  static constexpr int KLOC = TMP, KLS = 8;  // local body transforms (7 words in records of 8: b128 + b96)
+  static_assert(KLS >= 7 && KLS * Md::NB <= Ly::HSZ + 4 * Ly::NROW, "tree scratch must fit in H + rows");
   // the model blob (lane-indexed tables, constraint-row records) follows the env slices in
   // LDS when it fits, else it is read from global memory
   static constexpr int TAB = STRIDE * NWG;
   // step_kernel stages each env's hot state (the duck_layout fields before first_qpos) in LDS:
   // one batch of independent global loads in, one batch of stores out
-  static constexpr int HOT = Md::NQ + 2 * Md::NV + 8 * Md::NU + 77;
-  static constexpr int ESTRIDE = (HOT + 64) | 1;  // + the step's 64 random draws; odd: distinct banks
+  static constexpr int HOT = hot_words<Md>();
+  // + the step's 64 random draws; odd: distinct banks, so a pointer into the staged hot state must
+  // not carry the slices' alignment assumption
+  static constexpr int ESTRIDE = hot_stride(HOT);
+  static_assert(ESTRIDE % 2 == 1, "the staged hot state keeps its odd stride");
   static constexpr int ES_FLOATS = ESTRIDE * NWG;
   // latency modes: the cross-wave event counters, one 16-B word group each, in front of the slices'
   // end of LDS (LDS_FLOATS counts them); NEV_G per set of 4 envs (the paired kernel has two sets)
@@ -345,6 +350,7 @@ struct TLay {
   // (duck_env_kernels.h launch_step; AUTO then falls back, duck_set_step_mode refuses it)
   static constexpr bool FITS = (size_t)LDS_FLOATS * 4 <= 160 * 1024 && (LAT == 0 || (TAB_LDS && ES_LDS));
   static_assert(LAT || FITS, "LDS budget");
+  static_assert(LAT || lay_keeps<Md>(Ly::TOTAL) == TAB_LDS + 2 * HT_LDS + 4 * ES_LDS, "lay_keeps (duck_physics.h) and TLay agree");
   static_assert(6 * Md::NV <= 4 * Ly::NROW, "crb scratch must fit in the row storage");
   static_assert(LAT || 18 * Md::NB <= Ly::HSZ + 4 * Ly::NROW, "rne scratch must fit in H + rows");
   static_assert(LAT || Md::FLOOR_TYPE != 1 || XSIL + 2 * HF_SLSZ <= Ly::CIN + 10 * Md::NB,
@@ -425,7 +431,7 @@ struct TPhys {
   static constexpr int R_LIM = Ly::R_LIM, R_CON = Ly::R_CON;
   static DK int ti(int off) {
     if constexpr (TL::TAB_LDS) {
-      extern __shared__ float lds_dyn[];
+      extern __shared__ LDS_ALIGNED float lds_dyn[];
       return ((lds_int*)(lds_dyn + TL::TAB))[off];
     } else {
       return Md::t_blob()[off];
@@ -435,7 +441,7 @@ struct TPhys {
   // the hull SAT tables (blob words B_HFACE .. B_HEND): LDS whenever they fit
   static DK float th(int off) {
     if constexpr (!TL::TAB_LDS && TL::HT_LDS) {
-      extern __shared__ float lds_dyn[];
+      extern __shared__ LDS_ALIGNED float lds_dyn[];
       return ((lds_float*)(lds_dyn + TL::TAB))[off - Md::B_HFACE];
     } else {
       return tf(off);
@@ -445,7 +451,7 @@ struct TPhys {
   // the height-field scenes): the reads indexed per lane (the unrolled loops over all faces and
   // edges take the compile-time constants instead: as LDS reads they were 28 % slower)
   static DK f4v ht4(int off) {
-    extern __shared__ __attribute__((aligned(16))) float lds_dyn[];
+    extern __shared__ LDS_ALIGNED float lds_dyn[];
     static_assert(Md::FLOOR_TYPE != 1 || TL::TAB_LDS || TL::HT_LDS, "the hull SAT tables must be in LDS");
     return *(const lds_f4*)((lds_float*)lds_dyn + TL::TAB + (TL::TAB_LDS ? off : off - Md::B_HFACE));
   }
@@ -529,9 +535,9 @@ struct TPhys {
     q2m(R, q);
   }
   static DK void store_pose(LP L, int b, const float* p, const float* q, const float* R) {
-    for (int k = 0; k < 3; k++) L[Ly::XPOS + 3 * b + k] = p[k];
+    for (int k = 0; k < 3; k++) L[Ly::XPOS + Ly::XPS * b + k] = p[k];
     for (int k = 0; k < 4; k++) L[Ly::XQ + 4 * b + k] = q[k];
-    for (int k = 0; k < 9; k++) L[Ly::XMAT + 9 * b + k] = R[k];
+    for (int k = 0; k < 9; k++) L[Ly::XMAT + Ly::XMS * b + k] = R[k];
   }
 
   static DK void kinematics(LP L, int lane) {
@@ -554,8 +560,8 @@ struct TPhys {
           qmul(q, q, ql);
         }
       }
-      for (int k = 0; k < 4; k++) L[TL::KLOC + 7 * b + k] = q[k];
-      for (int k = 0; k < 3; k++) L[TL::KLOC + 7 * b + 4 + k] = tf(o + 4 + k);
+      for (int k = 0; k < 4; k++) L[TL::KLOC + TL::KLS * b + k] = q[k];
+      for (int k = 0; k < 3; k++) L[TL::KLOC + TL::KLS * b + 4 + k] = tf(o + 4 + k);
     });
     TSYNC();
     STAGE_MARK(24);
@@ -568,8 +574,8 @@ struct TPhys {
     if (lane == 0) store_pose(L, 1, p, q, R);
     auto compose = [&](int b) {
       float ql[4], pl[3], t[3], qn[4];
-      for (int k = 0; k < 4; k++) ql[k] = L[TL::KLOC + 7 * b + k];
-      for (int k = 0; k < 3; k++) pl[k] = L[TL::KLOC + 7 * b + 4 + k];
+      for (int k = 0; k < 4; k++) ql[k] = L[TL::KLOC + TL::KLS * b + k];
+      for (int k = 0; k < 3; k++) pl[k] = L[TL::KLOC + TL::KLS * b + 4 + k];
       mulmv3(t, R, pl);
       for (int k = 0; k < 3; k++) p[k] += t[k];
       qmul(qn, q, ql);
@@ -591,7 +597,7 @@ struct TPhys {
 #pragma unroll
       for (int d = 0; d < BL; d++) {
         const int bc = bb[d] >= 0 ? bb[d] : 1;
-        for (int k = 0; k < 7; k++) kl[d][k] = L[TL::KLOC + 7 * bc + k];
+        for (int k = 0; k < 7; k++) kl[d][k] = L[TL::KLOC + TL::KLS * bc + k];
       }
 #pragma unroll
       for (int d = 0; d < BL; d++) {
@@ -622,7 +628,7 @@ struct TPhys {
     if (mv) {
       const int ob = Md::B_BINERT + 17 * b;
       float R[9], t[3], ip[3], Ri[9], Bi[9];
-      for (int k = 0; k < 9; k++) R[k] = L[Ly::XMAT + 9 * b + k];
+      for (int k = 0; k < 9; k++) R[k] = L[Ly::XMAT + Ly::XMS * b + k];
       for (int k = 0; k < 3; k++) ip[k] = (b == 1) ? L[Ly::DIPOS + k] : tf(ob + k);
       for (int k = 0; k < 9; k++) Bi[k] = tf(ob + 3 + k);
       mulmv3(t, R, ip);
@@ -631,7 +637,7 @@ struct TPhys {
       for (int a = 0; a < 3; a++)
         for (int c = 0; c < 3; c++)
           rot[3 * a + c] = Ri[3 * a] * I[0] * Ri[3 * c] + Ri[3 * a + 1] * I[1] * Ri[3 * c + 1] + Ri[3 * a + 2] * I[2] * Ri[3 * c + 2];
-      for (int k = 0; k < 3; k++) xi[k] = L[Ly::XPOS + 3 * b + k] + t[k];
+      for (int k = 0; k < 3; k++) xi[k] = L[Ly::XPOS + Ly::XPS * b + k] + t[k];
       m = L[Ly::DMASS + b];
     }
     const float ms = tsum(m);
@@ -657,12 +663,12 @@ struct TPhys {
       // affine joint maps (codegen B_JAFF): hinge j >= B_JN0 sits on body j + B_JBD with dof j + B_JDD
       const bool jh = Md::B_JAFF && j >= Md::B_JN0;
       const int b = jh ? j + Md::B_JBD : ti(oj), da = jh ? j + Md::B_JDD : ti(oj + 1);
-      const float off[3] = {com[0] - L[Ly::XPOS + 3 * b], com[1] - L[Ly::XPOS + 3 * b + 1], com[2] - L[Ly::XPOS + 3 * b + 2]};
+      const float off[3] = {com[0] - L[Ly::XPOS + Ly::XPS * b], com[1] - L[Ly::XPOS + Ly::XPS * b + 1], com[2] - L[Ly::XPOS + Ly::XPS * b + 2]};
       if (!jh && ti(oj + 3) == 0) {
         for (int k = 0; k < 3; k++)
           for (int q = 0; q < 6; q++) L[Ly::CDOF + 6 * (da + k) + q] = (q == 3 + k) ? 1.0f : 0.0f;
         for (int k = 0; k < 3; k++) {
-          const float ax[3] = {L[Ly::XMAT + 9 * b + k], L[Ly::XMAT + 9 * b + 3 + k], L[Ly::XMAT + 9 * b + 6 + k]};
+          const float ax[3] = {L[Ly::XMAT + Ly::XMS * b + k], L[Ly::XMAT + Ly::XMS * b + 3 + k], L[Ly::XMAT + Ly::XMS * b + 6 + k]};
           float t[3];
           cross3(t, ax, off);
           const int o = Ly::CDOF + 6 * (da + 3 + k);
@@ -671,7 +677,7 @@ struct TPhys {
       } else {
         float R[9], ax[3], t[3];
         const float ja[3] = {tf(oj + 4), tf(oj + 5), tf(oj + 6)};
-        for (int k = 0; k < 9; k++) R[k] = L[Ly::XMAT + 9 * b + k];
+        for (int k = 0; k < 9; k++) R[k] = L[Ly::XMAT + Ly::XMS * b + k];
         mulmv3(ax, R, ja);
         cross3(t, ax, off);
         const int o = Ly::CDOF + 6 * da;
@@ -1406,8 +1412,8 @@ struct TPhys {
         const float sg = (e & 1) ? -mu : mu;
         float u[3], r3[3], a[6];
         for (int q = 0; q < 3; q++) {
-          u[q] = L[Ly::CFR + 9 * slot + q] + sg * L[Ly::CFR + 9 * slot + 3 * t + q];
-          r3[q] = L[Ly::CR + 3 * slot + q];
+          u[q] = L[Ly::CFR + Ly::CFS * slot + q] + sg * L[Ly::CFR + Ly::CFS * slot + 3 * t + q];
+          r3[q] = L[Ly::CR + Ly::CRS * slot + q];
         }
         cross3(a, r3, u);
         a[3] = u[0]; a[4] = u[1]; a[5] = u[2];
@@ -1470,8 +1476,8 @@ struct TPhys {
         const float sg = (e & 1) ? -mu : mu;
         float u[3], r3[3], a[6];
         for (int q = 0; q < 3; q++) {
-          u[q] = L[Ly::CFR + 9 * slot + q] + sg * L[Ly::CFR + 9 * slot + 3 * t + q];
-          r3[q] = L[Ly::CR + 3 * slot + q];
+          u[q] = L[Ly::CFR + Ly::CFS * slot + q] + sg * L[Ly::CFR + Ly::CFS * slot + 3 * t + q];
+          r3[q] = L[Ly::CR + Ly::CRS * slot + q];
         }
         cross3(a, r3, u);
         a[3] = u[0]; a[4] = u[1]; a[5] = u[2];
@@ -1525,10 +1531,10 @@ struct TPhys {
   static DK void cgeom_frame(LP L, int gs, float* gp, float* gR) {
     const int o = Md::B_CGEOM + 16 * gs, b = ti(o);
     float R[9], t[3], gpos[3], gm[9];
-    for (int k = 0; k < 9; k++) { R[k] = L[Ly::XMAT + 9 * b + k]; gm[k] = tf(o + 4 + k); }
+    for (int k = 0; k < 9; k++) { R[k] = L[Ly::XMAT + Ly::XMS * b + k]; gm[k] = tf(o + 4 + k); }
     for (int k = 0; k < 3; k++) gpos[k] = tf(o + 1 + k);
     mulmv3(t, R, gpos);
-    for (int k = 0; k < 3; k++) gp[k] = L[Ly::XPOS + 3 * b + k] + t[k];
+    for (int k = 0; k < 3; k++) gp[k] = L[Ly::XPOS + Ly::XPS * b + k] + t[k];
     mulmm3(gR, R, gm);
   }
 
@@ -2961,14 +2967,14 @@ struct TPhys {
     const int o = Md::B_PAIR + PAIRW * p;
     const int s1 = ti(o), s2 = ti(o + 1);
     const float mu = tf(o + 2);
-    const float r[3] = {L[Ly::CR + 3 * slot], L[Ly::CR + 3 * slot + 1], L[Ly::CR + 3 * slot + 2]};
+    const float r[3] = {L[Ly::CR + Ly::CRS * slot], L[Ly::CR + Ly::CRS * slot + 1], L[Ly::CR + Ly::CRS * slot + 2]};
     float v[3] = {0.0f, 0.0f, 0.0f}, t[3];
     if (s2 != 0) { Ph::contact_vel(s2 == 1 ? SL : SR, r, t); v[0] += t[0]; v[1] += t[1]; v[2] += t[2]; }
     if (s1 != 0) { Ph::contact_vel(s1 == 1 ? SL : SR, r, t); v[0] -= t[0]; v[1] -= t[1]; v[2] -= t[2]; }
     float jr[3];
     for (int q = 0; q < 3; q++)
-      jr[q] = L[Ly::CFR + 9 * slot + 3 * q] * v[0] + L[Ly::CFR + 9 * slot + 3 * q + 1] * v[1] +
-              L[Ly::CFR + 9 * slot + 3 * q + 2] * v[2];
+      jr[q] = L[Ly::CFR + Ly::CFS * slot + 3 * q] * v[0] + L[Ly::CFR + Ly::CFS * slot + 3 * q + 1] * v[1] +
+              L[Ly::CFR + Ly::CFS * slot + 3 * q + 2] * v[2];
     out4[0] = jr[0] + mu * jr[1];
     out4[1] = jr[0] - mu * jr[1];
     out4[2] = jr[0] + mu * jr[2];
@@ -3491,9 +3497,9 @@ struct TPhys {
       const int typ = ti(os), site = ti(os + 1), adr = ti(os + 2), b = ti(os + 3);
       float R[9], sp[3], sR[9], t[3], SM[9];
       const float spos[3] = {tf(os + 4), tf(os + 5), tf(os + 6)};
-      for (int k = 0; k < 9; k++) { R[k] = L[Ly::XMAT + 9 * b + k]; SM[k] = tf(os + 7 + k); }
+      for (int k = 0; k < 9; k++) { R[k] = L[Ly::XMAT + Ly::XMS * b + k]; SM[k] = tf(os + 7 + k); }
       mulmv3(t, R, spos);
-      for (int k = 0; k < 3; k++) sp[k] = L[Ly::XPOS + 3 * b + k] + t[k];
+      for (int k = 0; k < 3; k++) sp[k] = L[Ly::XPOS + Ly::XPS * b + k] + t[k];
       mulmm3(sR, R, SM);
       const float off[3] = {sp[0] - com[0], sp[1] - com[1], sp[2] - com[2]};
       float ang[3] = {L[Ly::CVEL + 6 * b], L[Ly::CVEL + 6 * b + 1], L[Ly::CVEL + 6 * b + 2]}, lin[3];
@@ -3656,12 +3662,12 @@ struct TPhys {
   static_assert(EV_TIMEOUT < TL::NEV_G || !LAT, "event slots");
   // the paired kernel (LAT 2): waves 2w and 2w + 1 work env set w, whose events are its own group
   static DK lds_int* ev_ptr(int k) {
-    extern __shared__ float lds_dyn[];
+    extern __shared__ LDS_ALIGNED float lds_dyn[];
     const int g = LAT == 2 ? __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 7) : 0;
     return (lds_int*)(lds_dyn + TL::EV) + 4 * (k + TL::NEV_G * g);
   }
   static DK void ev_init(int tid) {
-    extern __shared__ float lds_dyn[];
+    extern __shared__ LDS_ALIGNED float lds_dyn[];
     if (tid < TL::NEV) ((lds_int*)(lds_dyn + TL::EV))[4 * tid] = 0;
   }
   static DK void ev_signal(int k, int v) {
@@ -3688,7 +3694,7 @@ struct TPhys {
   }
   // did a wait of env set g give up (after the final barrier: every wave's waits are over)
   static DK bool ev_timed_out(int g) {
-    extern __shared__ float lds_dyn[];
+    extern __shared__ LDS_ALIGNED float lds_dyn[];
     return ((lds_int*)(lds_dyn + TL::EV))[4 * (EV_TIMEOUT + TL::NEV_G * g)] != 0;
   }
   // wave 0, substep s: kinematics and com_pos (everything else waits for them), rne's velocities

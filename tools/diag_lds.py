@@ -24,21 +24,64 @@ gen = os.path.join(os.path.dirname(__file__), "..", "open_duck_playground_amd", 
                     "rough_terrain": "duck_model_rough.h",
                     "rough_terrain_backlash": "duck_model_rough_backlash.h"}[task])
 txt = open(gen).read()
-C = {k: int(v) for k, v in re.findall(r"\b(NB|NQ|NV|NU|NM|MAXCHAIN|NSENSORDATA|NPAIR|NFRIC|NLIM|NHE|NHF|FLOOR_TYPE) = (\d+)", txt)}
+C = {k: int(v) for k, v in re.findall(r"\b(NB|NQ|NV|NU|NM|MAXCHAIN|NSENSORDATA|NPAIR|NFRIC|NLIM|NHE|NHF|FLOOR_TYPE|NBLOB|B_HFACE|B_HEND) = (\d+)", txt)}
 NB, NQ, NV, NU, NM = C["NB"], C["NQ"], C["NV"], C["NU"], C["NM"]
 NCON = 4 * C["NPAIR"]
-NROW = C["NFRIC"] + C["NLIM"] + 4 * NCON
+R_CON = C["NFRIC"] + C["NLIM"]
+NROW = R_CON + 4 * NCON
 # Lay::HSZ: the scratch in front of the rows, sized for its largest user
 need = max(12 * NB + 6 * NV, 6 * (C["NHE"] + C["NHF"]), 3 + 28 * 16 if C["FLOOR_TYPE"] == 1 else 0, 86 + 9 * NU)
 HSZ = (max(need - 4 * NROW - C["NLIM"], 0) + 3) // 4 * 4
-# Lay<Md> (csrc/duck_physics.h) in order
-fields = [("QPOS", NQ), ("QVEL", NV), ("WARM", NV), ("CTRL", NU), ("QACC", NV), ("QSM", NV), ("FSM", NV),
-          ("SRCH", NV), ("GRAD", NV), ("MA", NV), ("DMASS", NB), ("DIPOS", 3), ("DARM", NV), ("DFRIC", NV),
-          ("DQ0", NQ), ("DKP", NU), ("XPOS", 3 * NB), ("XQ", 4 * NB), ("XMAT", 9 * NB), ("CIN", 10 * NB),
-          ("CVEL", 6 * NB), ("COM", 3), ("CDOF", 6 * NV), ("CDD1", 18), ("M", NM), ("MZERO", 1), ("H", HSZ), ("JA", NROW),
-          ("JV", NROW), ("RD", NROW), ("AREF", NROW), ("LSGN", C["NLIM"]), ("CR", 3 * NCON), ("CFR", 9 * NCON),
-          ("CDIST", NCON), ("AF", NU), ("SENS", C["NSENSORDATA"]), ("OCON", 2), ("IMUR", 3), ("FOOTZ", 2),
-          ("FLAGS", 2), ("SINK", 32)]
+
+
+def lay_fields(al, wide):
+    """LayT<Md, AL, WIDE> (csrc/duck_physics.h): the fields in slice order, padding as "pad" entries."""
+    out, pos = [], [0]
+
+    def up(a):
+        pad = -pos[0] % min(al, a)
+        if pad:
+            out.append(("pad", pad))
+            pos[0] += pad
+
+    def put(name, k, a=1, shift=0):
+        pos[0] += shift
+        up(a)
+        pos[0] -= shift
+        out.append((name, k))
+        pos[0] += k
+
+    xps, xms, crs, cfs = (4, 10, 4, 10) if wide else (3, 9, 3, 9)
+    put("XQ", 4 * NB), put("XMAT", xms * NB), put("XPOS", xps * NB, 4), put("CIN", 10 * NB, 4), put("CVEL", 6 * NB, 4)
+    put("CDOF", 6 * NV, 4), put("M", NM, 4), put("MZERO", 1), put("CDD1", 18, 2), put("COM", 3, 4), put("IMUR", 3)
+    put("OCON", 2), put("FOOTZ", 2), put("FLAGS", 2), put("H", HSZ, 4)
+    for r in ("JA", "JV", "RD", "AREF"):
+        put(r, NROW, 4, R_CON)  # the contact rows (from R_CON on) start on a 4-float boundary
+    put("LSGN", C["NLIM"], 2), put("CR", crs * NCON, 4), put("CFR", cfs * NCON, 4), put("CDIST", NCON, 4)
+    put("AF", NU, 2), put("SENS", C["NSENSORDATA"], 2)
+    for name, k in (("QPOS", NQ), ("QVEL", NV), ("WARM", NV), ("CTRL", NU), ("QACC", NV), ("QSM", NV), ("FSM", NV),
+                    ("SRCH", NV), ("GRAD", NV), ("MA", NV), ("DMASS", NB), ("DIPOS", 3), ("DARM", NV), ("DFRIC", NV),
+                    ("DQ0", NQ), ("DKP", NU)):
+        put(name, k)
+    up(4)
+    return out, pos[0]
+
+
+def lay_keeps(total):
+    """duck_physics.h lay_keeps: what stays in LDS next to 16 slices of `total` words"""
+    W, tab = 160 * 1024 // 4, 16 * (((total + 32 + 15) // 32) * 32 + 16)
+    nht = max(C.get("B_HEND", 0) - C.get("B_HFACE", 0), 0)
+    tabl = tab + C["NBLOB"] <= W
+    htl = not tabl and nht > 0 and tab + nht <= W
+    es = tab + (C["NBLOB"] if tabl else (nht if htl else 0))
+    esl = es + 16 * ((NQ + 2 * NV + 8 * NU + 77 + 64) | 1) <= W
+    return -1 if es > W else tabl + 2 * htl + 4 * esl
+
+
+# Lay<Md>: the first rule whose slices keep in LDS what the packed ones keep (lay_rule)
+keep = lay_keeps(lay_fields(1, False)[1])
+al, wide = next((a, w) for w in (True, False) for a in (4, 2, 1) if lay_keeps(lay_fields(a, w)[1]) == keep)
+fields = lay_fields(al, wide)[0] + [("SINK", 32)]
 total = sum(k for _, k in fields)
 
 env = Joystick(task, num_envs=1, device="cuda:0", use_imitation=False)
@@ -60,8 +103,8 @@ o = 0
 for name, k in fields:
     x, y = a[:, o:o + k], b[:, o:o + k]
     o += k
-    if name in ("QPOS", "QVEL"):
-        continue  # the loop copy integrates after write_aux? (aux is written before euler)
+    if name in ("QPOS", "QVEL", "pad"):
+        continue  # padding is never written; the loop copy integrates after write_aux? (aux is written before euler)
     d = np.abs(x - y) / (1 + np.abs(x))
     d[~(np.isfinite(x) & np.isfinite(y) & (np.abs(x) < 1e20))] = 0.0  # never-written slots (world/floor bodies)
     bad = np.where(d.max(axis=1) > 1e-5)[0]
