@@ -48,8 +48,11 @@ const char* duck_last_error(void);
 int duck_layout_get(int nq, int nv, int nu, int imitation, int task, duck_layout* out);
 /* size in floats of the per-env debug record written by duck_physics_step(aux) */
 int duck_aux_size(const duck_sim* sim);
-/* debug: per-stage cycle counters of a -DDUCK_STAGE_PROF build (32 + 1024 x uint64: 32 stage counters, then per-wave cycles of the last launch; optionally
- * reset); DUCK_EUNSUPPORTED in a regular build */
+/* debug: the cycle counters of a -DDUCK_STAGE_PROF build into out[DUCK_STAGE_CYCLES_WORDS] (optionally
+ * reset): 60 stage counters (csrc/duck_measure.h names them), then three blocks of 1024 words for the
+ * first 1024 waves of the last launch: each wave's cycles, its wall-clock start, its wall-clock end.
+ * DUCK_EUNSUPPORTED in a regular build */
+#define DUCK_STAGE_CYCLES_WORDS 3132 /* 60 + 3 * 1024 */
 int duck_debug_stage_cycles(const duck_sim* sim, unsigned long long* out, int reset);
 
 /* Identity of a kernel specialisation: FNV-1a 64 over the float32-rounded model values the

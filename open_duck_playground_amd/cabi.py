@@ -19,6 +19,17 @@ _I = C.POINTER(C.c_int)
 _D = C.POINTER(C.c_double)
 
 
+def _duck_h_int(name: str) -> int:
+    import os
+    import re
+    text = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "duck.h")).read()
+    return int(re.search(rf"^#define {name} (\d+)", text, re.M).group(1))
+
+
+# words (uint64) of duck_debug_stage_cycles' buffer
+STAGE_CYCLES_WORDS = _duck_h_int("DUCK_STAGE_CYCLES_WORDS")
+
+
 class DuckModelDesc(C.Structure):
     _fields_ = [
         ("nq", C.c_int), ("nv", C.c_int), ("nu", C.c_int), ("nbody", C.c_int), ("njnt", C.c_int),

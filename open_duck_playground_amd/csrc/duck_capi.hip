@@ -291,7 +291,7 @@ int duck_debug_lat_timeouts(const duck_sim* s, unsigned* out, int reset) {
   return kVariants[s->variant]->lat_timeouts(out, reset);
 }
 
-// debug: per-stage cycle counters of a -DDUCK_STAGE_PROF build (DUCK_EUNSUPPORTED otherwise)
+// debug: the cycle counters of a stage-profile build into out[DUCK_STAGE_CYCLES_WORDS] (DUCK_EUNSUPPORTED otherwise)
 int duck_debug_stage_cycles(const duck_sim* s, unsigned long long* out, int reset) {
   if (!s || !out) return duck_fail(DUCK_EINVAL, "bad argument");
   return kVariants[s->variant]->stage_cycles(out, reset);

@@ -456,7 +456,7 @@ DK void step_env(const KArgs& A, int e, int lane, lds_float* L, const FA& F, con
   TSYNC();
   // physics (joystick.py:420)
   float* scr = A.scratch ? A.scratch + e : nullptr;
-  STAGE_MARK(29);
+  STAGE_MARK(ST_ENV_PRE);
   if constexpr (LAT) {
     // wave 0's share of each substep (the paired kernel: wave A's); the other waves run theirs in
     // step_kernel_lat. The env code below reads the last substep's state and sensors: wait for Euler
@@ -486,7 +486,7 @@ DK void step_env(const KArgs& A, int e, int lane, lds_float* L, const FA& F, con
   }
   write_obs_team<Md>(A, lane, L, F, SObs{L + Ly::H}, r, 0, imitation_i);
   TSYNC();
-  STAGE_MARK(30);
+  STAGE_MARK(ST_ENV_CONTACTS_OBS);
   // termination (joystick.py:483-485)
   float nanp = 0.0f;
   team_for<NQ>(lane, [&](int i) { nanp += isnan(L[Ly::QPOS + i]) ? 1.0f : 0.0f; });
@@ -641,7 +641,7 @@ DK void step_env(const KArgs& A, int e, int lane, lds_float* L, const FA& F, con
   F[Lo.truncation] = trunc;
   A.reward[e] = reward;
   A.done[e] = done;
-  STAGE_MARK(31);
+  STAGE_MARK(ST_ENV_TERM);
   // coalesced rows: lane k of the team stores elements k, k + 16, ...
   TSYNC();
   float* priv = A.priv + (size_t)e * Lo.priv_size;
@@ -666,7 +666,7 @@ DK void step_env(const KArgs& A, int e, int lane, lds_float* L, const FA& F, con
     const int k = lane + TEAM * kk;
     if (k < Lo.obs_size) obs[k] = pv[kk];
   }
-  STAGE_MARK(34);
+  STAGE_MARK(ST_ENV_OBS_STORE);
 }
 
 // the step's random stream: key and counter from the prefetch, the first RngTab::N draws made by
@@ -684,15 +684,13 @@ DK RngTab step_rng(const StepPre& P, lds_float* tab, int lane) {
 template <class Md>
 __global__ void __launch_bounds__(TPB) step_kernel(KArgs A) {
   STAGE_T0();
-#ifdef DUCK_ANY_PROF
-  const unsigned long long kstart = clock64(), kwall = wall_clock64();
-#endif
+  KERNEL_T0();
   using TL = TLay<Md>;
   {
     extern __shared__ LDS_ALIGNED float lds_t[];
     load_model_tables<Md>(lds_t);
   }
-  STAGE_MARK(14);
+  STAGE_MARK(ST_MODEL_COPY);
   int lane;
   const int t = local_env(lane);
   const int e = blockIdx.x * TEAM_WG + t;
@@ -725,14 +723,14 @@ __global__ void __launch_bounds__(TPB) step_kernel(KArgs A) {
       }
     }
     __syncthreads();
-    STAGE_MARK(32);
+    STAGE_MARK(ST_ENV_HOT_LOAD);
     if (e < n) {
       lds_float* const L = env_slice<Md>(lds, t);
       const Col G{A.fs + e, n};  // global row: the auto-reset snapshot (first_*) stays in HBM
       lds_float* esp = (lds_float*)(lds + TL::ES + t * TL::ESTRIDE);
       const RngTab rt = step_rng(P, esp + TL::HOT, lane);
       TSYNC();
-      STAGE_MARK(33);
+      STAGE_MARK(ST_ENV_RNG);
       step_env<Md>(A, e, lane, L, LCol{esp}, G, rt, P);
       STAGE_RESET();
     }
@@ -763,15 +761,8 @@ __global__ void __launch_bounds__(TPB) step_kernel(KArgs A) {
     step_env<Md>(A, e, lane, L, G, G, r, step_prefetch<Md>(A, e, lane));
     STAGE_RESET();  // (no staged hot state to store: mark 15 counts nothing on this path)
   }
-  STAGE_MARK(15);
-#ifdef DUCK_ANY_PROF
-  if ((threadIdx.x & 63) == 0 && blockIdx.x < 256) {
-    const int w = 4 * blockIdx.x + threadIdx.x / 64;
-    g_stage_cycles[DUCK_NSTAGE + w] = clock64() - kstart;
-    g_stage_cycles[DUCK_NSTAGE + 1024 + w] = kwall;
-    g_stage_cycles[DUCK_NSTAGE + 2048 + w] = wall_clock64();
-  }
-#endif
+  STAGE_MARK(ST_ENV_HOT_STORE);
+  KERNEL_T1();
 }
 
 // Latency mode (duck_set_step_mode / DUCK_STEP_LATENCY, or AUTO at <= 4 envs per CU): 4 envs per
@@ -1090,25 +1081,7 @@ static int lat_timeouts_of(unsigned* out, int reset) {
   return e == hipSuccess ? DUCK_OK : duck_fail(DUCK_EHIP, hipGetErrorString(e));
 }
 
-static int stage_cycles_of(unsigned long long* out, int reset) {
-#ifdef DUCK_ANY_PROF
-  hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stage_cycles), sizeof(unsigned long long) * (DUCK_NSTAGE + 3 * 1024));
-  static unsigned long long wg[DUCK_NSTAGE * 256];
-  if (e == hipSuccess) e = hipMemcpyFromSymbol(wg, HIP_SYMBOL(g_stage_wg), sizeof(wg));
-  for (int k = 0; k < DUCK_NSTAGE && e == hipSuccess; k++)
-    for (int b = 0; b < 256; b++) out[k] += wg[k * 256 + b];
-  if (e == hipSuccess && reset) {
-    static unsigned long long z[DUCK_NSTAGE * 256 > DUCK_NSTAGE + 3 * 1024 ? DUCK_NSTAGE * 256 : DUCK_NSTAGE + 3 * 1024] = {0};
-    e = hipMemcpyToSymbol(HIP_SYMBOL(g_stage_cycles), z, sizeof(unsigned long long) * (DUCK_NSTAGE + 3 * 1024));
-    if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(g_stage_wg), z, sizeof(wg));
-  }
-  return e == hipSuccess ? 0 : DUCK_EHIP;
-#else
-  (void)out;
-  (void)reset;
-  return DUCK_EUNSUPPORTED;
-#endif
-}
+// (stage_cycles_of, behind duck_debug_stage_cycles: duck_measure.h)
 
 // one VariantOps table per compiled model (a host function, so the device pass skips it)
 // What each shipped scene keeps in LDS, pinned: a layout change (padding, record strides) that pushed

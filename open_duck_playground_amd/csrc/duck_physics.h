@@ -12,6 +12,7 @@
 #pragma once
 #include "../../include/duck_env.h"
 #include "duck_math.h"
+#include "duck_measure.h"
 
 #define DNI __device__ __noinline__
 // compiler-only barrier: stops the scheduler from hoisting a whole unrolled loop's LDS
@@ -35,69 +36,6 @@ DK lds_float* lds_assume16(lds_float* p) {
   return p;
 }
 
-// optional per-stage cycle counters (build with -DDUCK_STAGE_PROF; read by duck_debug_stage_cycles);
-// -DDUCK_WAVE_PROF records only the per-wave launch cycles (no stage marks perturbing wave 0)
-#if defined(DUCK_STAGE_PROF) || defined(DUCK_WAVE_PROF) || defined(DUCK_LAT_PROF)
-#define DUCK_ANY_PROF 1
-#endif
-#ifdef DUCK_ANY_PROF
-#define DUCK_NSTAGE 60
-static __device__ unsigned long long g_stage_cycles[DUCK_NSTAGE + 3 * 1024];
-// the stage counters themselves are kept per workgroup slot (summed by the host): one shared
-// counter per stage made every workgroup's atomics contend at one L2 channel, which slowed whole
-// XCDs by up to 30 % in profiled runs
-static __device__ unsigned long long g_stage_wg[DUCK_NSTAGE * 256];
-#define STAGE_ADD(k, v) atomicAdd(&g_stage_wg[(k) * 256 + (blockIdx.x & 255)], (v))
-#endif
-#ifdef DUCK_STAGE_PROF
-// g_stage_cycles: [0, DUCK_NSTAGE) stage counters; then per wave of the first 1024: clock64 cycles,
-// wall-clock (s_memrealtime, 100 MHz) start, wall-clock end; [DUCK_NSTAGE, DUCK_NSTAGE + 1024) cycles of each of the first 1024 waves
-// of the last step_kernel launch (wave = 4 * workgroup + wave-in-workgroup), for the launch tail
-#define STAGE_T0() unsigned long long _t0 = wall_clock64(), _c0 = clock64()
-#define STAGE_RESET() (_c0 = clock64())
-#define STAGE_MARK(k)                                                             \
-  do {                                                                            \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                            \
-    const unsigned long long _c1 = clock64();                                     \
-    if (threadIdx.x == 0) STAGE_ADD(k, _c1 - _c0);                                \
-    _c0 = _c1;                                                                    \
-    (void)_t0;                                                                    \
-  } while (0)
-#elif defined(DUCK_LAT_PROF)
-// latency-kernel builds (tools/lat_prof.py): each stage's cycles summed over the launch in workgroup 0
-// (lane 0 of the wave that runs it; in the latency kernel every stage runs on one wave) into
-// g_stage_cycles[DUCK_NSTAGE + 64 + k]; the waits between stages are outside every stage
-#define STAGE_T0() unsigned long long _c0 = clock64()
-#define STAGE_RESET() (_c0 = clock64())
-#define STAGE_MARK(k)                                                                  \
-  do {                                                                                 \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                 \
-    const unsigned long long _c1 = clock64();                                          \
-    if (blockIdx.x == 0 && ((int)threadIdx.x & 63) == 0) g_stage_cycles[DUCK_NSTAGE + 64 + (k)] += _c1 - _c0; \
-    _c0 = _c1;                                                                         \
-  } while (0)
-#elif defined(DUCK_ASM_MARKS)
-// static instruction counts per stage (tools/isa_stage_hist.py on hipcc -S output): a comment
-// at each stage boundary, no code
-#define STAGE_T0() \
-  do {             \
-  } while (0)
-#define STAGE_MARK(k) asm volatile("; STAGE_MARK " #k ::: "memory")
-#define STAGE_RESET() \
-  do {                \
-  } while (0)
-#else
-#define STAGE_T0() \
-  do {             \
-  } while (0)
-#define STAGE_MARK(k) \
-  do {                \
-  } while (0)
-#define STAGE_RESET() \
-  do {                \
-  } while (0)
-#endif
-
 // the longest privileged observation row (Joystick with imitation: duck_layout_make's priv_size);
 // the state row is its prefix (write_obs_team, duck_env_kernels.h)
 constexpr int priv_row_max(int nu) { return DUCK_OBS_SIZE(nu) + 15 + 3 * nu + 1 + 2 + 6 + 2 + 40 + 1 + 2; }
@@ -108,12 +46,7 @@ constexpr int priv_row_max(int nu) { return DUCK_OBS_SIZE(nu) + 15 + 3 * nu + 1 
 // the slices alone do not fit. The same sums as TLay<Md, 0> (duck_team.h), which asserts that they agree.
 constexpr int LDS_WORDS = 160 * 1024 / 4;
 constexpr int SLICES_WG = 16;  // env slices per throughput workgroup (= TEAM_WG)
-// per-lane dump slots after the Lay fields (TLay::SINK, 2 x TEAM words; debug line-search dumps use 136)
-#ifdef DUCK_LS_DUMP
-constexpr int SINK_WORDS = 136;
-#else
-constexpr int SINK_WORDS = 32;
-#endif
+// (SINK_WORDS: the per-lane dump slots after the Lay fields, TLay::SINK; duck_measure.h)
 constexpr int slice_stride(int used) { return ((used + 15) / 32) * 32 + 16; }  // = 16 (mod 32), >= used
 // step_kernel's staged hot state (the duck_layout fields before first_qpos) + the step's 64 random draws
 template <class Md>
@@ -139,10 +72,6 @@ constexpr int lay_keeps(int total) {
 // pad up to AL floats. A scene gets the even record strides (WIDE) and AL = 4 where such slices leave
 // in LDS what packed ones do (lay_keeps), else what of it fits (lay_rule): rough + backlash has 9 words
 // a slice to spare, and the same order without padding still puts most records on their boundaries.
-// (-DDUCK_LAY_WIDE=0: every scene with the odd record strides, for A/B builds)
-#ifndef DUCK_LAY_WIDE
-#define DUCK_LAY_WIDE 1
-#endif
 template <class Md, int AL, bool WIDE>
 struct LayT {
   static constexpr int ALIGN = AL, WIDE_RECORDS = WIDE;
@@ -214,11 +143,9 @@ struct LayT {
 template <class Md>
 constexpr int lay_rule() {
   constexpr int keep = lay_keeps<Md>(LayT<Md, 1, false>::TOTAL);
-  if (DUCK_LAY_WIDE) {
-    if (lay_keeps<Md>(LayT<Md, 4, true>::TOTAL) == keep) return 8 + 4;
-    if (lay_keeps<Md>(LayT<Md, 2, true>::TOTAL) == keep) return 8 + 2;
-    if (lay_keeps<Md>(LayT<Md, 1, true>::TOTAL) == keep) return 8 + 1;
-  }
+  if (lay_keeps<Md>(LayT<Md, 4, true>::TOTAL) == keep) return 8 + 4;
+  if (lay_keeps<Md>(LayT<Md, 2, true>::TOTAL) == keep) return 8 + 2;
+  if (lay_keeps<Md>(LayT<Md, 1, true>::TOTAL) == keep) return 8 + 1;
   return lay_keeps<Md>(LayT<Md, 4, false>::TOTAL) == keep ? 4 : (lay_keeps<Md>(LayT<Md, 2, false>::TOTAL) == keep ? 2 : 1);
 }
 template <class Md>
@@ -423,18 +350,13 @@ struct Phys {
     for (int s = 0; s < NCON; s++)
       for (int a = 0; a < 3; a++) aux[(o++) * stride] = L[Ly::CFR + Ly::CFS * s + a];  // contact normal
     for (int k = 0; k < Md::NM; k++) aux[(o++) * stride] = L[Ly::M + k];
-#ifdef DUCK_AUX_LDS
     // debug builds: the whole env slice (Lay fields + the per-lane dump slots; tools/diag_lds.py)
-    for (int k = 0; k < Ly::TOTAL + SINK_WORDS; k++) aux[(o++) * stride] = L[k];
-#endif
+    if constexpr (AUX_LDS)
+      for (int k = 0; k < Ly::TOTAL + SINK_WORDS; k++) aux[(o++) * stride] = L[k];
   }
 };
 
 template <class Md>
 constexpr int aux_size() {
-  return 4 * Md::NV + Md::NU + Md::NSENSORDATA + 7 * Lay<Md>::NCON + Md::NM
-#ifdef DUCK_AUX_LDS
-         + Lay<Md>::TOTAL + SINK_WORDS
-#endif
-      ;
+  return 4 * Md::NV + Md::NU + Md::NSENSORDATA + 7 * Lay<Md>::NCON + Md::NM + (AUX_LDS ? Lay<Md>::TOTAL + SINK_WORDS : 0);
 }

@@ -241,10 +241,8 @@ DK float cfma(float x, float a) {
 constexpr float HF_WITNESS_BAND = 1e-3f;
 // depths within this (m) of the deepest prism contact count as equal (oracle HF_DEPTH_TIE)
 constexpr float HF_DEPTH_TIE = 1e-6f;
-
-#ifndef DUCK_LS_DFLOOR
-#define DUCK_LS_DFLOOR 1e-6f
-#endif
+// the line search's fp32 termination floor, relative to its starting slope (TPhys::newton)
+constexpr float LS_SLOPE_FLOOR = 1e-6f;
 
 // Latency mode (LAT, step_kernel_lat): the stages of one substep are split over the four waves of a
 // workgroup that all work the same 4 envs (wave 0: kinematics, com_pos, rne, actuation and the env
@@ -255,25 +253,6 @@ constexpr float HF_DEPTH_TIE = 1e-6f;
 constexpr int LAT_WG = 4;  // envs (teams) per latency-mode workgroup: 4 waves x 4 teams, one team set per wave
 // latency-mode event waits that gave up (TPhys::ev_wait; read by duck_debug_lat_timeouts, must stay 0)
 static __device__ unsigned int g_lat_timeouts;
-// -DDUCK_LAT_PROF (tools/lat_prof.py): clock64 of each cross-wave event of substep 5 in workgroup 0, into
-// the per-wave cycle slots of g_stage_cycles (which only the throughput kernel writes)
-#ifdef DUCK_LAT_PROF
-#define LAT_T(k, s)                                                                                         \
-  do {                                                                                                      \
-    if (blockIdx.x == 0 && ((int)threadIdx.x & 63) == 0 && (s) == 5) g_stage_cycles[DUCK_NSTAGE + (k)] = clock64(); \
-  } while (0)
-#define LAT2_T(k, s)               \
-  do {                             \
-    if (threadIdx.x < 128) LAT_T(k, s); \
-  } while (0)
-#else
-#define LAT_T(k, s) \
-  do {              \
-  } while (0)
-#define LAT2_T(k, s) \
-  do {               \
-  } while (0)
-#endif
 
 // LAT: 0 = the throughput kernel (one team per env, 16 envs per workgroup); 1 = the latency kernel
 // (4 envs per workgroup, each substep's stages over 4 waves); 2 = the paired latency kernel (8 envs per
@@ -564,7 +543,7 @@ struct TPhys {
       for (int k = 0; k < 3; k++) L[TL::KLOC + TL::KLS * b + 4 + k] = tf(o + 4 + k);
     });
     TSYNC();
-    STAGE_MARK(24);
+    STAGE_MARK(ST_KIN_LOCAL);
     // K2: compose down the root path (every lane) and the limbs (a limb per lane)
     float p[3], q[4], R[9];
     for (int k = 0; k < 3; k++) p[k] = L[Ly::QPOS + k];
@@ -778,7 +757,7 @@ struct TPhys {
       }
     }
     TSYNC();
-    STAGE_MARK(21);
+    STAGE_MARK(ST_RNE_A);
   }
   template <int PART>
   static DK void rne_rest(LP L, int lane) {
@@ -796,7 +775,7 @@ struct TPhys {
       for (int k = 0; k < 6; k++) L[RFB + 6 * b + k] = f[k] + t2[k];
     });
     TSYNC();
-    STAGE_MARK(22);
+    STAGE_MARK(ST_RNE_B);
     // (C) subtree sums of the body forces (rne) and of the body inertias (mj_crb's composite
     // inertias, which overwrite CIN: phase B has read the body inertias), a component per lane:
     // lane k < 6 sums force component k, lane 6 + j inertia component j, down every limb from its
@@ -871,7 +850,7 @@ struct TPhys {
         }
         tot = m == 0 ? acc : tot + acc;
       }
-      STAGE_MARK(35);
+      STAGE_MARK(ST_RNE_LIMB);
 #pragma unroll
       for (int r = NR - 1; r >= 0; r--) {
         const int b = Md::T_ROOT[r];
@@ -880,7 +859,7 @@ struct TPhys {
       }
     }
     TSYNC();
-    STAGE_MARK(36);
+    STAGE_MARK(ST_RNE_ROOT);
   }
 
   // ---------------- mj_crb: the sparse M from the composite inertias (summed in rne) ----
@@ -889,10 +868,8 @@ struct TPhys {
     STAGE_T0();
     constexpr int BL = Md::T_BRLEN, MC = Md::MAXCHAIN;
     // (the composite inertias were summed in rne's subtree pass)
-    STAGE_MARK(19);
-#ifdef DUCK_ASM_MARKS
-    asm volatile("; CRB_BEGIN" ::: "memory");
-#endif
+    STAGE_MARK(ST_CRB_SUMS);
+    ASM_MARK("CRB_BEGIN");
     L[lane == 0 ? Ly::MZERO : TL::SINK + lane] = 0.0f;  // the zero word load_cols reads (LDS is not
                                                           // initialised by the launch)
     // M row i (lane i, i + 16): F_i = crb_{body(i)} cdof_i stays in registers;
@@ -977,9 +954,7 @@ struct TPhys {
 
   // ---------------- actuation + passive; H = M ----------------
   static DK void smooth(LP L, int lane) {
-#ifdef DUCK_ASM_MARKS
-    asm volatile("; SMOOTH_BEGIN" ::: "memory");
-#endif
+    ASM_MARK("SMOOTH_BEGIN");
     team_for<NV>(lane, [&](int i) { L[Ly::FSM + i] += -tf(Md::B_DAMP + i) * L[Ly::QVEL + i]; });
     TSYNC();
     if (lane < NU) {
@@ -1389,7 +1364,7 @@ struct TPhys {
 #pragma unroll
       for (int r = 0; r < NV; r++) F.col[s][r] = r >= TEAM * s ? Mc[s][r] + (r == c ? diag : 0.0f) : 0.0f;
     }
-    STAGE_MARK(16);
+    STAGE_MARK(ST_NEWTON_GRAD);
     // contact rows of each floor pair: per-foot 6x6 J'DJ block and J'force. Lanes 0-7 take the
     // 16 rows of side 0's pair, lanes 8-15 side 1's (two rows per lane), each half sums its
     // 27 values over 8 lanes; each side's sums are then broadcast from lane 0 or 8
@@ -1513,10 +1488,10 @@ struct TPhys {
         }
       }
     }
-    STAGE_MARK(17);
+    STAGE_MARK(ST_NEWTON_JDJ);
     if constexpr (FF) factor_solve_dense(F, g, lane);
     else factor_solve(F, g, lane);
-    STAGE_MARK(18);
+    STAGE_MARK(ST_NEWTON_FACTOR);
 #pragma unroll
     for (int s = 0; s < NC; s++) {
       const int c = TEAM * s + lane;
@@ -1740,14 +1715,6 @@ struct TPhys {
   // the contact point (oracle: the penetration-weighted centroid of the vertices of each shape
   // inside the other, or the midpoint of the support features). Writes (depth, normal, point)
   // over the entry's first 8 floats; depth -1 when separated.
-#ifdef DUCK_DOUBLE
-  // (measurement builds: values the compiler must treat as changed, so that a doubled stage is recomputed)
-  template <int N>
-  static DK void launder(float* x) {
-#pragma unroll
-    for (int i = 0; i < N; i++) asm volatile("" : "+v"(x[i]));
-  }
-#endif
   static DK void hf_exec(lds_float* E, LP L, int tw) {
     STAGE_T0();
     constexpr int NH = Md::NHV, NF = Md::NHF, NE = Md::NHE;
@@ -1758,12 +1725,13 @@ struct TPhys {
     const float GX = DYC * GN, GY = DXC * GN;
     lds_f4* E4 = (lds_f4*)E;
     const f4v d0 = E4[0], d1 = E4[1], d2 = E4[2], d3 = E4[3], d4 = E4[4], d5 = E4[5], d6 = E4[6];
-    const float Tm[3][3] = {{d0.x, d0.y, d0.z}, {d1.x, d1.y, d1.z}, {d2.x, d2.y, d2.z}};
+    // (Tm, ntm, zc: not const, the doubling builds launder them in place)
+    float Tm[3][3] = {{d0.x, d0.y, d0.z}, {d1.x, d1.y, d1.z}, {d2.x, d2.y, d2.z}};
     const float base = d0.w;
     float mo = d1.w;
     int mp = __float_as_int(d2.w);
     const int tag = __float_as_int(d3.w), tri = tag & 1, foot = tag >> 1;
-    const float ntm[3] = {d3.x, d3.y, d3.z}, zc[3] = {d4.x, d4.y, d4.z};
+    float ntm[3] = {d3.x, d3.y, d3.z}, zc[3] = {d4.x, d4.y, d4.z};
     const float xc[3] = {d5.x, d5.y, d5.z}, yc[3] = {d6.x, d6.y, d6.z};
     // the prism's side normals (triangle kind A: -x, (g_x, g_y), -y; B: -(g_x, g_y), +x, +y)
     float sm[3][3];
@@ -1792,19 +1760,8 @@ struct TPhys {
     };
     // the hull's faces (compile-time normals): the prism's lowest point along n_f, a bottom vertex
     // where n_f leans up the field's z (priority 5 + f; mu is formed after the SAT for these)
-#if defined(DUCK_DOUBLE) && DUCK_DOUBLE == 20
-    for (int rep_ = 0; rep_ < 2; rep_++)
-#endif
-    {
-#if defined(DUCK_DOUBLE) && DUCK_DOUBLE == 20
-      float Tm_l[3][3], zc_l[3] = {zc[0], zc[1], zc[2]};
-      for (int k = 0; k < 3; k++)
-        for (int a = 0; a < 3; a++) Tm_l[k][a] = Tm[k][a];
-      launder<9>(&Tm_l[0][0]);
-      launder<3>(zc_l);
-      const auto& Tm = Tm_l;
-      const auto& zc = zc_l;
-#endif
+    STAGE_TWICE(20) {
+      STAGE_FRESH(20, Tm, zc);
       const float hk[3] = {d4.w - base, d5.w - base, d6.w - base};
       static_for<0, NF>([&](auto fI) {
         constexpr int f = fI.value;
@@ -1830,10 +1787,7 @@ struct TPhys {
       for (int a = 0; a < 3; a++) mu[a] = b ? u[a] : mu[a];
     };
     // vertical-edge pairs: the prism's support along w is its vertical edge at vertex kk
-#if defined(DUCK_DOUBLE) && DUCK_DOUBLE == 15
-    for (int rep_ = 0; rep_ < 2; rep_++)
-#endif
-    {
+    STAGE_TWICE(15) {
       const lds_float* SL = L + ((foot >> 1) - tw) * TL::STRIDE + HF_CINQ + (foot & 1) * HF_SLSZ;
       const lds_int* SLi = (const lds_int*)SL;
       const lds_f4* SLw = (const lds_f4*)(SL + HF_SLF);
@@ -1853,26 +1807,15 @@ struct TPhys {
         take(fmaxf(q0, fmaxf(q1, q2)) - w.w, HF_PRIO_V + 3 * e + kk, wv);
       }
     }
-    STAGE_MARK(44);
+    STAGE_MARK(ST_SAT_VERTICAL);
     // top-edge pairs (hull edge e, prism top edge k: faces ntm, sm_k). Pass 1: the arcs cross when
     // CBA DBA < 0, ADC BDC < 0 and CBA BDC > 0 (C = -n_a, D = -n_b, B x A = sm_k x ntm: CBA =
     // -phi_a), all three products negative: the sign bit of their maximum, bit q = NE k + e of pm.
     // The bits are shifted into 32-bit words in q order (one v_alignbit per pair; placing each bit
     // at its position took a shift, a mask and an or) and bit-reversed into pm afterwards
     unsigned long long pm[3] = {0ull, 0ull, 0ull};
-#if defined(DUCK_DOUBLE) && DUCK_DOUBLE == 12
-    for (int rep_ = 0; rep_ < 2; rep_++)
-#endif
-    {
-#if defined(DUCK_DOUBLE) && DUCK_DOUBLE == 12
-      float ntm_l[3] = {ntm[0], ntm[1], ntm[2]}, sm_l[3][3];
-      for (int k = 0; k < 3; k++)
-        for (int a = 0; a < 3; a++) sm_l[k][a] = sm[k][a];
-      launder<3>(ntm_l);
-      launder<9>(&sm_l[0][0]);
-      const auto& ntm = ntm_l;
-      const auto& sm = sm_l;
-#endif
+    STAGE_TWICE(12) {
+      STAGE_FRESH(12, ntm, sm);
       constexpr int NQW = (3 * NE + 31) / 32;
       unsigned qw[NQW];
 #pragma unroll
@@ -1913,57 +1856,51 @@ struct TPhys {
         pm[j >> 1] |= (unsigned long long)r << (32 * (j & 1));
       });
     }
-    STAGE_MARK(45);
-#ifdef DUCK_STAGE_PROF
-    if (threadIdx.x < 64) {
-      // crossing top-edge pairs: all of the wave's survivors (49), hull edges crossing in any of them (50)
-      STAGE_ADD(49, (unsigned long long)(__popcll(pm[0]) + __popcll(pm[1]) + __popcll(pm[2])));
-      int uni = 0;
-      for (int e = 0; e < NE; e++) {
-        unsigned long long b3 = 0ull;
-        for (int k = 0; k < 3; k++) b3 |= (pm[(NE * k + e) >> 6] >> ((NE * k + e) & 63)) & 1ull;
-        uni += __ballot(b3 != 0ull) != 0ull;
+    STAGE_MARK(ST_SAT_PASS1);
+    if constexpr (STAGE_PROF) {
+      // crossing top-edge pairs: all of wave 0's survivors, and its hull edges crossing in any of them
+      if (threadIdx.x < 64) {
+        STAGE_COUNT(ST_N_HF_PAIRS, (unsigned long long)(__popcll(pm[0]) + __popcll(pm[1]) + __popcll(pm[2])));
+        int uni = 0;
+        for (int e = 0; e < NE; e++) {
+          unsigned long long b3 = 0ull;
+          for (int k = 0; k < 3; k++) b3 |= (pm[(NE * k + e) >> 6] >> ((NE * k + e) & 63)) & 1ull;
+          uni += __ballot(b3 != 0ull) != 0ull;
+        }
+        STAGE_COUNT_WAVE0(ST_N_HF_EDGES, (unsigned long long)uni);
       }
-      if ((int)threadIdx.x == __ffsll((long long)__ballot(1)) - 1) STAGE_ADD(50, (unsigned long long)uni);
     }
-#endif
-    // pass 2: each crossing pair's overlap along ev x em
-#if defined(DUCK_DOUBLE) && DUCK_DOUBLE == 11
-    const unsigned long long pm_s[3] = {pm[0], pm[1], pm[2]};
-    for (int rep_ = 0; rep_ < 2; rep_++) {
-      for (int w = 0; w < 3; w++) pm[w] = pm_s[w];
-#endif
-    while (pm[0] | pm[1] | pm[2]) {
-#ifdef DUCK_STAGE_PROF
-      if (threadIdx.x < 64 && (int)threadIdx.x == __ffsll((long long)__ballot(1)) - 1) STAGE_ADD(48, 1ull);
-#endif
-      const bool z0 = pm[0] == 0ull, z1 = pm[1] == 0ull;
-      const unsigned long long w = z0 ? (z1 ? pm[2] : pm[1]) : pm[0];
-      const int q = (z0 ? (z1 ? 128 : 64) : 0) + __builtin_ctzll(w);
-      const unsigned long long wc = w & (w - 1ull);
-      pm[0] = z0 ? pm[0] : wc;
-      pm[1] = z0 && !z1 ? wc : pm[1];
-      pm[2] = z0 && z1 ? wc : pm[2];
-      // (the pairs run in q order; the minimum over (overlap, priority p) does not depend on it)
-      const int k = q >= 2 * NE ? 2 : (q >= NE ? 1 : 0), e = q - NE * k, p = 3 * e + k, o = Md::B_HEDGE + 20 * e;
-      const f4v ev4 = ht4(o + 12), v04 = ht4(o + 16);
-      const float ev[3] = {ev4.x, ev4.y, ev4.z}, v0[3] = {v04.x, v04.y, v04.z};
-      float em[3], tm[3], sk[3];
-      side(k, sk);
-      top_edge(k, tm, em);
-      float u[3];
-      cross3(u, ev, em);
-      const float u2 = dot3(u, u);
-      const float sg = (dot3(u, ntm) + dot3(u, sk) < 0.0f ? -1.0f : 1.0f) * __builtin_amdgcn_rsqf(u2);
-      const float un[3] = {sg * u[0], sg * u[1], sg * u[2]};
-      // (a degenerate pair, ev parallel to em, gives no axis; ev4.w = |ev|^2)
-      const float ov = u2 >= 1e-12f * ev4.w * dot3(em, em) ? sg * (dot3(u, tm) - dot3(u, v0)) : 1e30f;
-      take(ov, HF_PRIO_T + p, un);
+    // pass 2: each crossing pair's overlap along ev x em (it consumes pm)
+    STAGE_KEEP(11, pm);
+    STAGE_TWICE(11) {
+      STAGE_RESTORE(11, pm);
+      while (pm[0] | pm[1] | pm[2]) {
+        STAGE_COUNT_WAVE0(ST_N_HF_PASS2_ITERS, 1ull);
+        const bool z0 = pm[0] == 0ull, z1 = pm[1] == 0ull;
+        const unsigned long long w = z0 ? (z1 ? pm[2] : pm[1]) : pm[0];
+        const int q = (z0 ? (z1 ? 128 : 64) : 0) + __builtin_ctzll(w);
+        const unsigned long long wc = w & (w - 1ull);
+        pm[0] = z0 ? pm[0] : wc;
+        pm[1] = z0 && !z1 ? wc : pm[1];
+        pm[2] = z0 && z1 ? wc : pm[2];
+        // (the pairs run in q order; the minimum over (overlap, priority p) does not depend on it)
+        const int k = q >= 2 * NE ? 2 : (q >= NE ? 1 : 0), e = q - NE * k, p = 3 * e + k, o = Md::B_HEDGE + 20 * e;
+        const f4v ev4 = ht4(o + 12), v04 = ht4(o + 16);
+        const float ev[3] = {ev4.x, ev4.y, ev4.z}, v0[3] = {v04.x, v04.y, v04.z};
+        float em[3], tm[3], sk[3];
+        side(k, sk);
+        top_edge(k, tm, em);
+        float u[3];
+        cross3(u, ev, em);
+        const float u2 = dot3(u, u);
+        const float sg = (dot3(u, ntm) + dot3(u, sk) < 0.0f ? -1.0f : 1.0f) * __builtin_amdgcn_rsqf(u2);
+        const float un[3] = {sg * u[0], sg * u[1], sg * u[2]};
+        // (a degenerate pair, ev parallel to em, gives no axis; ev4.w = |ev|^2)
+        const float ov = u2 >= 1e-12f * ev4.w * dot3(em, em) ? sg * (dot3(u, tm) - dot3(u, v0)) : 1e30f;
+        take(ov, HF_PRIO_T + p, un);
+      }
     }
-#if defined(DUCK_DOUBLE) && DUCK_DOUBLE == 11
-    }
-#endif
-    STAGE_MARK(47);
+    STAGE_MARK(ST_SAT_PASS2);
     if (!(mo > 0.0f)) {
       E4[0] = f4v{-1.0f, 0.0f, 0.0f, 0.0f};
       return;
@@ -1979,105 +1916,88 @@ struct TPhys {
     }
     // the contact point: hull vertices inside the prism and prism top vertices inside the hull,
     // weighted by their penetration
-#if defined(DUCK_DOUBLE) && DUCK_DOUBLE == 13
-    for (int rep_ = 0; rep_ < 2; rep_++) {
-      float Tm_l[3][3], sm_l[3][3], ntm_l[3] = {ntm[0], ntm[1], ntm[2]}, zc_l[3] = {zc[0], zc[1], zc[2]};
-      float mu_l[3] = {mu[0], mu[1], mu[2]};
-      for (int k = 0; k < 3; k++)
-        for (int a = 0; a < 3; a++) Tm_l[k][a] = Tm[k][a], sm_l[k][a] = sm[k][a];
-      launder<9>(&Tm_l[0][0]);
-      launder<9>(&sm_l[0][0]);
-      launder<3>(ntm_l);
-      launder<3>(zc_l);
-      launder<3>(mu_l);
-      const auto& Tm = Tm_l;
-      const auto& sm = sm_l;
-      const auto& ntm = ntm_l;
-      const auto& zc = zc_l;
-      const auto& mu = mu_l;
-#endif
-    const float ptop = dot3(ntm, Tm[0]);
-    const float smt[3] = {dot3(sm[0], Tm[0]), dot3(sm[1], Tm[1]), dot3(sm[2], Tm[2])};
-    float W = 0.0f, Cx[3] = {0.0f, 0.0f, 0.0f};
-    // (every vertex, without a wave-uniform skip of those above every lane's prism top: the 17
-    // branches cost more than the distances they skipped, C4 -0.8 %; the weights are the same)
-    static_for<0, NH>([&](auto kI) {
-      constexpr int k = kI.value;
-      // (o - v_k . x with the offset fused into the first product, v_fmamk_f32, measured C4 +0.7 % and
-      // C5 +0.9 %, but moved the teacher-forced outliers: rough + DR seeds 7 / 11 / 13 / 17 10 / 24 /
-      // 16 / 12 of 10,240 with one unexplained, against 13 / 20 / 14 / 13 all explained -- not kept)
-      float d[5];
-      hv_dot5<k>(ntm, zc, sm[0], sm[1], sm[2], d);
-      const float atop = ptop - d[0];
-      float pen = fminf(atop, d[1] - base);
-      for (int j = 0; j < 3; j++) pen = fminf(pen, smt[j] - d[2 + j]);
-      const float w = fmaxf(pen, 0.0f);
-      W += w;
-      Cx[0] = cfma<fbits(Md::hull_vert[k][0])>(w, Cx[0]);
-      Cx[1] = cfma<fbits(Md::hull_vert[k][1])>(w, Cx[1]);
-      Cx[2] = cfma<fbits(Md::hull_vert[k][2])>(w, Cx[2]);
-    });
-    {
-      // the prism's top vertices inside the hull: the faces in HullFaceOrder, and once no lane of the
-      // wave has a vertex still inside every face tested so far (checked after the first 6 and 14),
-      // the rest are skipped -- every weight is 0 then, and the minimum is order-independent
-      float pk[3] = {1e30f, 1e30f, 1e30f};
-      bool live = true;
-      static_for<0, NF>([&](auto pI) {
-        constexpr int pos = pI.value;
-        constexpr int f = HullFaceOrder<Md>{}.f[pos];
-        if (pos == 6 || pos == 14) live = live && __ballot(fmaxf(pk[0], fmaxf(pk[1], pk[2])) > 0.0f) != 0ull;
-        if (!live) return;
-        float d[3];
-        nf_off_dot3<f>(Tm[0], Tm[1], Tm[2], d);
-#pragma unroll
-        for (int j = 0; j < 3; j++) pk[j] = fminf(pk[j], d[j]);
-      });
-#pragma unroll
-      for (int j = 0; j < 3; j++) {
-        const float w = fmaxf(pk[j], 0.0f);
-        W += w;
-        for (int a = 0; a < 3; a++) Cx[a] += w * Tm[j][a];
-      }
-    }
-    float pos[3];
-    if (W > 0.0f) {
-      const float iw = 1.0f / W;
-      for (int a = 0; a < 3; a++) pos[a] = Cx[a] * iw;
-    } else {
-      // no vertex inside at all (crossing edges): the midpoint of the two shapes' support features
-      // along mu. (Round 4 blended towards it below a total weight of 1e-4 m -- a "point band" for
-      // onset prisms; fp32 and fp64 then disagreed 2-3x as often)
-      float hmu = 1e30f;
-      float hv[NH];
-      static_for<0, NH>([&](auto kI) { hv[kI.value] = hv_dot<kI.value>(mu); });
-#pragma unroll
-      for (int k = 0; k < NH; k++) hmu = fminf(hmu, hv[k]);
-      float wh_ = 0.0f, ch[3] = {0.0f, 0.0f, 0.0f};
+    STAGE_TWICE(13) {
+      STAGE_FRESH(13, Tm, sm, ntm, zc, mu);
+      const float ptop = dot3(ntm, Tm[0]);
+      const float smt[3] = {dot3(sm[0], Tm[0]), dot3(sm[1], Tm[1]), dot3(sm[2], Tm[2])};
+      float W = 0.0f, Cx[3] = {0.0f, 0.0f, 0.0f};
+      // (every vertex, without a wave-uniform skip of those above every lane's prism top: the 17
+      // branches cost more than the distances they skipped, C4 -0.8 %; the weights are the same)
       static_for<0, NH>([&](auto kI) {
         constexpr int k = kI.value;
-        const float w = fmaxf(0.0f, 1.0f - (hv[k] - hmu) * (1.0f / HF_WITNESS_BAND));
-        wh_ += w;
-        ch[0] = cfma<fbits(Md::hull_vert[k][0])>(w, ch[0]);
-        ch[1] = cfma<fbits(Md::hull_vert[k][1])>(w, ch[1]);
-        ch[2] = cfma<fbits(Md::hull_vert[k][2])>(w, ch[2]);
+        // (o - v_k . x with the offset fused into the first product, v_fmamk_f32, measured C4 +0.7 % and
+        // C5 +0.9 %, but moved the teacher-forced outliers: rough + DR seeds 7 / 11 / 13 / 17 10 / 24 /
+        // 16 / 12 of 10,240 with one unexplained, against 13 / 20 / 14 / 13 all explained -- not kept)
+        float d[5];
+        hv_dot5<k>(ntm, zc, sm[0], sm[1], sm[2], d);
+        const float atop = ptop - d[0];
+        float pen = fminf(atop, d[1] - base);
+        for (int j = 0; j < 3; j++) pen = fminf(pen, smt[j] - d[2 + j]);
+        const float w = fmaxf(pen, 0.0f);
+        W += w;
+        Cx[0] = cfma<fbits(Md::hull_vert[k][0])>(w, Cx[0]);
+        Cx[1] = cfma<fbits(Md::hull_vert[k][1])>(w, Cx[1]);
+        Cx[2] = cfma<fbits(Md::hull_vert[k][2])>(w, Cx[2]);
       });
-      const float q[3] = {dot3(mu, Tm[0]), dot3(mu, Tm[1]), dot3(mu, Tm[2])};
-      const float pmx = fmaxf(q[0], fmaxf(q[1], q[2]));
-      float wp_ = 0.0f, cq[3] = {0.0f, 0.0f, 0.0f};
-      for (int k = 0; k < 3; k++) {
-        const float w = fmaxf(0.0f, 1.0f - (pmx - q[k]) * (1.0f / HF_WITNESS_BAND));
-        wp_ += w;
-        for (int a = 0; a < 3; a++) cq[a] += w * Tm[k][a];
+      {
+        // the prism's top vertices inside the hull: the faces in HullFaceOrder, and once no lane of the
+        // wave has a vertex still inside every face tested so far (checked after the first 6 and 14),
+        // the rest are skipped -- every weight is 0 then, and the minimum is order-independent
+        float pk[3] = {1e30f, 1e30f, 1e30f};
+        bool live = true;
+        static_for<0, NF>([&](auto pI) {
+          constexpr int pos = pI.value;
+          constexpr int f = HullFaceOrder<Md>{}.f[pos];
+          if (pos == 6 || pos == 14) live = live && __ballot(fmaxf(pk[0], fmaxf(pk[1], pk[2])) > 0.0f) != 0ull;
+          if (!live) return;
+          float d[3];
+          nf_off_dot3<f>(Tm[0], Tm[1], Tm[2], d);
+  #pragma unroll
+          for (int j = 0; j < 3; j++) pk[j] = fminf(pk[j], d[j]);
+        });
+  #pragma unroll
+        for (int j = 0; j < 3; j++) {
+          const float w = fmaxf(pk[j], 0.0f);
+          W += w;
+          for (int a = 0; a < 3; a++) Cx[a] += w * Tm[j][a];
+        }
       }
-      const float iwh = frcp(wh_), iwp = frcp(wp_);
-      for (int a = 0; a < 3; a++) pos[a] = 0.5f * (ch[a] * iwh + cq[a] * iwp);
+      float pos[3];
+      if (W > 0.0f) {
+        const float iw = 1.0f / W;
+        for (int a = 0; a < 3; a++) pos[a] = Cx[a] * iw;
+      } else {
+        // no vertex inside at all (crossing edges): the midpoint of the two shapes' support features
+        // along mu. (Round 4 blended towards it below a total weight of 1e-4 m -- a "point band" for
+        // onset prisms; fp32 and fp64 then disagreed 2-3x as often)
+        float hmu = 1e30f;
+        float hv[NH];
+        static_for<0, NH>([&](auto kI) { hv[kI.value] = hv_dot<kI.value>(mu); });
+  #pragma unroll
+        for (int k = 0; k < NH; k++) hmu = fminf(hmu, hv[k]);
+        float wh_ = 0.0f, ch[3] = {0.0f, 0.0f, 0.0f};
+        static_for<0, NH>([&](auto kI) {
+          constexpr int k = kI.value;
+          const float w = fmaxf(0.0f, 1.0f - (hv[k] - hmu) * (1.0f / HF_WITNESS_BAND));
+          wh_ += w;
+          ch[0] = cfma<fbits(Md::hull_vert[k][0])>(w, ch[0]);
+          ch[1] = cfma<fbits(Md::hull_vert[k][1])>(w, ch[1]);
+          ch[2] = cfma<fbits(Md::hull_vert[k][2])>(w, ch[2]);
+        });
+        const float q[3] = {dot3(mu, Tm[0]), dot3(mu, Tm[1]), dot3(mu, Tm[2])};
+        const float pmx = fmaxf(q[0], fmaxf(q[1], q[2]));
+        float wp_ = 0.0f, cq[3] = {0.0f, 0.0f, 0.0f};
+        for (int k = 0; k < 3; k++) {
+          const float w = fmaxf(0.0f, 1.0f - (pmx - q[k]) * (1.0f / HF_WITNESS_BAND));
+          wp_ += w;
+          for (int a = 0; a < 3; a++) cq[a] += w * Tm[k][a];
+        }
+        const float iwh = frcp(wh_), iwp = frcp(wp_);
+        for (int a = 0; a < 3; a++) pos[a] = 0.5f * (ch[a] * iwh + cq[a] * iwp);
+      }
+      E4[0] = f4v{mo, mu[0], mu[1], mu[2]};
+      E4[1] = f4v{pos[0], pos[1], pos[2], 0.0f};
     }
-    E4[0] = f4v{mo, mu[0], mu[1], mu[2]};
-    E4[1] = f4v{pos[0], pos[1], pos[2], 0.0f};
-#if defined(DUCK_DOUBLE) && DUCK_DOUBLE == 13
-    }
-#endif
   }
 
   // the grid offsets (column, row) of top vertex k of a cell's triangle: A (tri 0) = (0, 0), (0, 1), (1, 0);
@@ -2109,7 +2029,7 @@ struct TPhys {
       const float d[3] = {cp[0] - pp[0], cp[1] - pp[1], cp[2] - pp[2]};
       mulmtv3(t, PR, d);
     }
-    const float zc[3] = {R[6], R[7], R[8]};  // the field's z axis in the mesh frame
+    float zc[3] = {R[6], R[7], R[8]};  // the field's z axis in the mesh frame (not const: doubling launders it)
     // this lane's hull vertices (local) and the hull's bounding box
     float xl[VPL][3];
     bool vok[VPL];
@@ -2207,15 +2127,8 @@ struct TPhys {
     // order into the env slice's composite-inertia storage (dead after crb()): the direction w in
     // which the negated arc crosses the equator and the hull's support along it
     lds_float* const SLo = L + HF_CINQ + h * HF_SLSZ;
-#if defined(DUCK_DOUBLE) && DUCK_DOUBLE == 17
-    for (int rep_ = 0; rep_ < 2; rep_++)
-#endif
-    {
-#if defined(DUCK_DOUBLE) && DUCK_DOUBLE == 17
-      float zc_l[3] = {zc[0], zc[1], zc[2]};
-      launder<3>(zc_l);
-      const auto& zc = zc_l;
-#endif
+    STAGE_TWICE(17) {
+      STAGE_FRESH(17, zc);
       unsigned long long M = 0;
       float wv[EPL][3], wh[EPL];
       bool sl[EPL];
@@ -2254,64 +2167,58 @@ struct TPhys {
     float smo[PPL], szt[PPL][3];
     int smp[PPL];
     unsigned surv = 0;
-#if defined(DUCK_DOUBLE) && DUCK_DOUBLE == 14
-    for (int rep_ = 0; rep_ < 2; rep_++) {
-      launder<9>(R);
-      launder<GPL>(zg);
-      launder<3>(lo);
-#endif
-#pragma unroll
-    for (int j = 0; j < PPL; j++) {
-      const int q = sub + 8 * j;
-      smo[j] = 0.0f;
-      smp[j] = 0;
-      for (int k = 0; k < 3; k++) szt[j][k] = 0.0f;
-      // (a wave-uniform skip of the slots no foot of the wave has: most sub-grids hold <= 12 prisms)
-      if (j > 0 && __ballot(q < np) == 0ull) continue;
-      float T[3][3], nt[3];
-      int tri;
-      prism_top(q < np ? q : 0, T, tri);
-      top_normal(T, nt);
-      float ntm[3];
-      mulmtv3(ntm, R, nt);
-      float hm = 1e30f;
-      // (vertex pairs: two interleaved products per statement; the minimum is order-independent)
-      static_for<0, NH / 2>([&](auto kI) {
-        float ha, hb;
-        hv_dot2<2 * kI.value>(ntm, ha, hb);
-        hm = fmin_nc(hm, fmin_nc(ha, hb));
-      });
-      if constexpr (NH % 2) hm = fminf(hm, hv_dot<NH - 1>(ntm));
-      // priority order (equal overlaps: the first): top 0, sides 1-3, bottom 4, hull faces 5 + f
-      float mo = dot3(nt, T[0]) - hm;
-      int mp = 0;
-      for (int k = 0; k < 3; k++) {  // (tri is 0 or 1: two-way selects, not an indexed register array)
-        const float sxk = tri ? sx_[1][k] : sx_[0][k], syk = tri ? sy_[1][k] : sy_[0][k];
-        const float ov = sxk * T[k][0] + syk * T[k][1] - (tri ? smin[1][k] : smin[0][k]);
-        mp = ov < mo ? 1 + k : mp;
-        mo = fminf(mo, ov);
+    STAGE_TWICE(14) {
+      STAGE_FRESH(14, R, zg, lo);
+  #pragma unroll
+      for (int j = 0; j < PPL; j++) {
+        const int q = sub + 8 * j;
+        smo[j] = 0.0f;
+        smp[j] = 0;
+        for (int k = 0; k < 3; k++) szt[j][k] = 0.0f;
+        // (a wave-uniform skip of the slots no foot of the wave has: most sub-grids hold <= 12 prisms)
+        if (j > 0 && __ballot(q < np) == 0ull) continue;
+        float T[3][3], nt[3];
+        int tri;
+        prism_top(q < np ? q : 0, T, tri);
+        top_normal(T, nt);
+        float ntm[3];
+        mulmtv3(ntm, R, nt);
+        float hm = 1e30f;
+        // (vertex pairs: two interleaved products per statement; the minimum is order-independent)
+        static_for<0, NH / 2>([&](auto kI) {
+          float ha, hb;
+          hv_dot2<2 * kI.value>(ntm, ha, hb);
+          hm = fmin_nc(hm, fmin_nc(ha, hb));
+        });
+        if constexpr (NH % 2) hm = fminf(hm, hv_dot<NH - 1>(ntm));
+        // priority order (equal overlaps: the first): top 0, sides 1-3, bottom 4, hull faces 5 + f
+        float mo = dot3(nt, T[0]) - hm;
+        int mp = 0;
+        for (int k = 0; k < 3; k++) {  // (tri is 0 or 1: two-way selects, not an indexed register array)
+          const float sxk = tri ? sx_[1][k] : sx_[0][k], syk = tri ? sy_[1][k] : sy_[0][k];
+          const float ov = sxk * T[k][0] + syk * T[k][1] - (tri ? smin[1][k] : smin[0][k]);
+          mp = ov < mo ? 1 + k : mp;
+          mo = fminf(mo, ov);
+        }
+        mp = obot < mo ? 4 : mp;
+        mo = fminf(mo, obot);
+        // (the hull's 30 face axes are the survivors' first SAT step, hf_exec: per survivor lane once,
+        // instead of per screened prism slot -- they separate ≈ 0.6 prisms per foot-substep more)
+        const bool high = !(T[0][2] < lo[2] && T[1][2] < lo[2] && T[2][2] < lo[2]);
+        const bool ok = q < np && high && mo > 0.0f;
+        surv |= half_bits(__ballot(ok), lane) << (8 * j);
+        smo[j] = mo;
+        smp[j] = mp;
+        for (int k = 0; k < 3; k++) szt[j][k] = T[k][2];
       }
-      mp = obot < mo ? 4 : mp;
-      mo = fminf(mo, obot);
-      // (the hull's 30 face axes are the survivors' first SAT step, hf_exec: per survivor lane once,
-      // instead of per screened prism slot -- they separate ≈ 0.6 prisms per foot-substep more)
-      const bool high = !(T[0][2] < lo[2] && T[1][2] < lo[2] && T[2][2] < lo[2]);
-      const bool ok = q < np && high && mo > 0.0f;
-      surv |= half_bits(__ballot(ok), lane) << (8 * j);
-      smo[j] = mo;
-      smp[j] = mp;
-      for (int k = 0; k < 3; k++) szt[j][k] = T[k][2];
     }
-#if defined(DUCK_DOUBLE) && DUCK_DOUBLE == 14
-    }
-#endif
     float cd[PPL], cn[PPL][3], cx[PPL][3];  // this lane's prism contacts: depth, normal, point (local)
 #pragma unroll
     for (int s = 0; s < PPL; s++) {
       cd[s] = -1.0f;
       for (int a = 0; a < 3; a++) { cn[s][a] = 0.0f; cx[s][a] = 0.0f; }
     }
-    STAGE_MARK(37);
+    STAGE_MARK(ST_HF_SCREEN);
     // 2. the survivors of the wave's 8 feet, one per lane: a queue in the H + constraint-row
     // storage of the wave's 4 env slices (dead until make_rows()), entry g in slice g & 3; each
     // lane writes its survivors' descriptors (mesh frame), every active lane runs one entry's SAT
@@ -2329,64 +2236,58 @@ struct TPhys {
       }
     }
     const int nact = __popcll(act), QRa = nact < HF_QR ? nact : HF_QR;
-#ifdef DUCK_STAGE_PROF
-    if (threadIdx.x == 0) STAGE_ADD(40, (unsigned long long)S);
+    STAGE_COUNT_IF(threadIdx.x == 0, ST_N_HF_SURVIVORS, (unsigned long long)S);
     // the survivors' distribution over wave-substeps (wave 0): <= 21, 22-32, 33-42, 43-64, > 64
-    if (threadIdx.x == 0) STAGE_ADD(S <= 21 ? 51 : (S <= 32 ? 52 : (S <= 42 ? 53 : (S <= 64 ? 54 : 55))), 1ull);
-#endif
+    STAGE_COUNT_IF(threadIdx.x == 0,
+                   S <= 21   ? ST_N_HF_SURV_LE21
+                   : S <= 32 ? ST_N_HF_SURV_LE32
+                   : S <= 42 ? ST_N_HF_SURV_LE42
+                   : S <= 64 ? ST_N_HF_SURV_LE64
+                             : ST_N_HF_SURV_GT64,
+                   1ull);
     const int gi = __popcll(act & ((1ull << ((int)threadIdx.x & 63)) - 1ull));  // this lane among the active
     auto qent = [&](int g) -> lds_float* { return L + ((g & 3) - tw) * TL::STRIDE + HF_QH0 + HF_ENT * (g >> 2); };
     for (int r0 = 0; r0 < S; r0 += QRa) {
-#ifdef DUCK_STAGE_PROF
-      if (threadIdx.x == 0) STAGE_ADD(46, 1ull);
-#endif
-#if defined(DUCK_DOUBLE) && DUCK_DOUBLE == 18
-      for (int rep_ = 0; rep_ < 2; rep_++) {
-      launder<9>(R);
-#endif
-#pragma unroll
-      for (int j = 0; j < PPL; j++) {
-        const int q = sub + 8 * j;
-        const int g = g0 + __popc(surv & ((1u << q) - 1u)) - r0;
-        const bool mine = ((surv >> q) & 1u) && g >= 0 && g < QRa;
-        if (__ballot(mine) == 0ull) continue;
-        if (mine) {
-          // the prism's top (local) as the screen had it, then the mesh frame
-          const int rr = q / (2 * ncx), rem = q - rr * 2 * ncx, cc = rem >> 1, tri = rem & 1;
-          float T[3][3], nt[3], ntm[3], Tm[3][3];
-#pragma unroll
-          for (int k = 0; k < 3; k++) {
-            T[k][0] = X0 + (float)(cc + tri_dc(k, tri)) * DXC;
-            T[k][1] = Y0 + (float)(rr + tri_dr(k, tri)) * DYC;
-            T[k][2] = szt[j][k];
+      STAGE_COUNT_IF(threadIdx.x == 0, ST_N_HF_ROUNDS, 1ull);
+      STAGE_TWICE(18) {
+        STAGE_FRESH(18, R);
+  #pragma unroll
+        for (int j = 0; j < PPL; j++) {
+          const int q = sub + 8 * j;
+          const int g = g0 + __popc(surv & ((1u << q) - 1u)) - r0;
+          const bool mine = ((surv >> q) & 1u) && g >= 0 && g < QRa;
+          if (__ballot(mine) == 0ull) continue;
+          if (mine) {
+            // the prism's top (local) as the screen had it, then the mesh frame
+            const int rr = q / (2 * ncx), rem = q - rr * 2 * ncx, cc = rem >> 1, tri = rem & 1;
+            float T[3][3], nt[3], ntm[3], Tm[3][3];
+  #pragma unroll
+            for (int k = 0; k < 3; k++) {
+              T[k][0] = X0 + (float)(cc + tri_dc(k, tri)) * DXC;
+              T[k][1] = Y0 + (float)(rr + tri_dr(k, tri)) * DYC;
+              T[k][2] = szt[j][k];
+            }
+            top_normal(T, nt);
+            mulmtv3(ntm, R, nt);
+            for (int k = 0; k < 3; k++) mulmtv3(Tm[k], R, T[k]);
+            lds_f4* E4 = (lds_f4*)qent(g);
+            E4[0] = f4v{Tm[0][0], Tm[0][1], Tm[0][2], base};
+            E4[1] = f4v{Tm[1][0], Tm[1][1], Tm[1][2], smo[j]};
+            E4[2] = f4v{Tm[2][0], Tm[2][1], Tm[2][2], __int_as_float(smp[j])};
+            E4[3] = f4v{ntm[0], ntm[1], ntm[2], __int_as_float(tri | (2 * tw + h) << 1)};
+            E4[4] = f4v{zc[0], zc[1], zc[2], szt[j][0]};
+            E4[5] = f4v{R[0], R[1], R[2], szt[j][1]};
+            E4[6] = f4v{R[3], R[4], R[5], szt[j][2]};
           }
-          top_normal(T, nt);
-          mulmtv3(ntm, R, nt);
-          for (int k = 0; k < 3; k++) mulmtv3(Tm[k], R, T[k]);
-          lds_f4* E4 = (lds_f4*)qent(g);
-          E4[0] = f4v{Tm[0][0], Tm[0][1], Tm[0][2], base};
-          E4[1] = f4v{Tm[1][0], Tm[1][1], Tm[1][2], smo[j]};
-          E4[2] = f4v{Tm[2][0], Tm[2][1], Tm[2][2], __int_as_float(smp[j])};
-          E4[3] = f4v{ntm[0], ntm[1], ntm[2], __int_as_float(tri | (2 * tw + h) << 1)};
-          E4[4] = f4v{zc[0], zc[1], zc[2], szt[j][0]};
-          E4[5] = f4v{R[0], R[1], R[2], szt[j][1]};
-          E4[6] = f4v{R[3], R[4], R[5], szt[j][2]};
         }
       }
-#if defined(DUCK_DOUBLE) && DUCK_DOUBLE == 18
-      }
-#endif
       TSYNC();
-      STAGE_MARK(41);
-#ifdef DUCK_ASM_MARKS
-      asm volatile("; HF_EXEC_BEGIN" ::: "memory");
-#endif
+      STAGE_MARK(ST_HFQ_DESC);
+      ASM_MARK("HF_EXEC_BEGIN");
       if (gi < QRa && r0 + gi < S) hf_exec(qent(gi), L, tw);
-#ifdef DUCK_ASM_MARKS
-      asm volatile("; HF_EXEC_END" ::: "memory");
-#endif
+      ASM_MARK("HF_EXEC_END");
       TSYNC();
-      STAGE_MARK(42);
+      STAGE_MARK(ST_HFQ_SAT);
 #pragma unroll
       for (int j = 0; j < PPL; j++) {
         const int q = sub + 8 * j;
@@ -2403,148 +2304,142 @@ struct TPhys {
         }
       }
       TSYNC();
-      STAGE_MARK(43);
+      STAGE_MARK(ST_HFQ_GATHER);
     }
-    STAGE_MARK(38);
+    STAGE_MARK(ST_HF_QUEUE);
     // 4 slots by mjx's _manifold_points over the prism contacts, from the deepest (the first prism
     // within HF_DEPTH_TIE of it: prisms sharing a grid vertex or edge often tie exactly); index
     // q = sub + 8 s is the prism's strip position
-#if defined(DUCK_DOUBLE) && DUCK_DOUBLE == 19
-    for (int rep_ = 0; rep_ < 2; rep_++) {
-    launder<PPL>(cd);
-    launder<3 * PPL>(&cx[0][0]);
-    launder<3 * PPL>(&cn[0][0]);
-#endif
-    constexpr int QN = 8 * PPL;
-    float dmax = -1e30f;
-#pragma unroll
-    for (int s = 0; s < PPL; s++) dmax = fmaxf(dmax, cd[s] > 0.0f ? cd[s] : -1e30f);
-    dmax = hmax8_nc(dmax);
-    const bool any = dmax > 0.0f;
-    int a_ = 1 << 20;
-#pragma unroll
-    for (int s = PPL - 1; s >= 0; s--)
-      a_ = ((cd[s] > 0.0f) & (cd[s] >= dmax - HF_DEPTH_TIE)) ? sub + 8 * s : a_;  // (& : selects, not branches)
-    a_ = hmin8i(a_);
-    a_ = a_ < QN ? a_ : 0;
-    // a contact's fields, fetched from its owner lane (q uniform over the half-team)
-    auto fetch = [&](int q, float* x, float* n, float& d) {
-      float px[3], pn[3], pd = cd[0];
-      for (int a = 0; a < 3; a++) { px[a] = cx[0][a]; pn[a] = cn[0][a]; }
-#pragma unroll
-      for (int s = 1; s < PPL; s++) {
-        const bool m = (q >> 3) == s;
-        pd = m ? cd[s] : pd;
-        for (int a = 0; a < 3; a++) { px[a] = m ? cx[s][a] : px[a]; pn[a] = m ? cn[s][a] : pn[a]; }
-      }
-      const int src = 8 * h + (q & 7);
-      d = __shfl(pd, src, TEAM);
-      for (int a = 0; a < 3; a++) { x[a] = __shfl(px[a], src, TEAM); n[a] = __shfl(pn[a], src, TEAM); }
-    };
-    // argmax with mjx's tolerance: the first index within tol of the maximum (valid contacts only)
-    auto argmax = [&](const float* v, float tol) -> int {
-      float mx = -1e30f;
-#pragma unroll
-      for (int s = 0; s < PPL; s++) mx = fmaxf(mx, v[s]);
-      mx = hmax8_nc(mx);
-      int best = 1 << 20;
-#pragma unroll
+    STAGE_TWICE(19) {
+      STAGE_FRESH(19, cd, cx, cn);
+      constexpr int QN = 8 * PPL;
+      float dmax = -1e30f;
+  #pragma unroll
+      for (int s = 0; s < PPL; s++) dmax = fmaxf(dmax, cd[s] > 0.0f ? cd[s] : -1e30f);
+      dmax = hmax8_nc(dmax);
+      const bool any = dmax > 0.0f;
+      int a_ = 1 << 20;
+  #pragma unroll
       for (int s = PPL - 1; s >= 0; s--)
-        best = ((cd[s] > 0.0f) & (v[s] >= mx - tol)) ? sub + 8 * s : best;
-      best = hmin8i(best);
-      return best < QN ? best : a_;
-    };
-    float pa[3], na[3], da, sc[PPL];
-    fetch(a_, pa, na, da);
-#pragma unroll
-    for (int s = 0; s < PPL; s++) {
-      const float dx = pa[0] - cx[s][0], dy = pa[1] - cx[s][1], dz = pa[2] - cx[s][2];
-      sc[s] = cd[s] > 0.0f ? dx * dx + dy * dy + dz * dz : -1e30f;
-    }
-    const int b_ = argmax(sc, MANIFOLD_TOL);
-    float pb[3], nb[3], db;
-    fetch(b_, pb, nb, db);
-    float ab[3];
-    {
-      const float amb[3] = {pa[0] - pb[0], pa[1] - pb[1], pa[2] - pb[2]};
-      cross3(ab, na, amb);
-    }
-#pragma unroll
-    for (int s = 0; s < PPL; s++) {
-      const float ap[3] = {pa[0] - cx[s][0], pa[1] - cx[s][1], pa[2] - cx[s][2]};
-      sc[s] = cd[s] > 0.0f ? fabsf(dot3(ap, ab)) : -1e30f;
-    }
-    const int c_ = argmax(sc, MANIFOLD_TOL);
-    float pc[3], nc_[3], dcc;
-    fetch(c_, pc, nc_, dcc);
-    float ac[3], bc[3];
-    {
-      const float amc[3] = {pa[0] - pc[0], pa[1] - pc[1], pa[2] - pc[2]};
-      const float bmc[3] = {pb[0] - pc[0], pb[1] - pc[1], pb[2] - pc[2]};
-      cross3(ac, na, amc);
-      cross3(bc, na, bmc);
-    }
-    int d_;
-    {
-      float s1[PPL], s2[PPL], mx = -1e30f;
-#pragma unroll
+        a_ = ((cd[s] > 0.0f) & (cd[s] >= dmax - HF_DEPTH_TIE)) ? sub + 8 * s : a_;  // (& : selects, not branches)
+      a_ = hmin8i(a_);
+      a_ = a_ < QN ? a_ : 0;
+      // a contact's fields, fetched from its owner lane (q uniform over the half-team)
+      auto fetch = [&](int q, float* x, float* n, float& d) {
+        float px[3], pn[3], pd = cd[0];
+        for (int a = 0; a < 3; a++) { px[a] = cx[0][a]; pn[a] = cn[0][a]; }
+  #pragma unroll
+        for (int s = 1; s < PPL; s++) {
+          const bool m = (q >> 3) == s;
+          pd = m ? cd[s] : pd;
+          for (int a = 0; a < 3; a++) { px[a] = m ? cx[s][a] : px[a]; pn[a] = m ? cn[s][a] : pn[a]; }
+        }
+        const int src = 8 * h + (q & 7);
+        d = __shfl(pd, src, TEAM);
+        for (int a = 0; a < 3; a++) { x[a] = __shfl(px[a], src, TEAM); n[a] = __shfl(pn[a], src, TEAM); }
+      };
+      // argmax with mjx's tolerance: the first index within tol of the maximum (valid contacts only)
+      auto argmax = [&](const float* v, float tol) -> int {
+        float mx = -1e30f;
+  #pragma unroll
+        for (int s = 0; s < PPL; s++) mx = fmaxf(mx, v[s]);
+        mx = hmax8_nc(mx);
+        int best = 1 << 20;
+  #pragma unroll
+        for (int s = PPL - 1; s >= 0; s--)
+          best = ((cd[s] > 0.0f) & (v[s] >= mx - tol)) ? sub + 8 * s : best;
+        best = hmin8i(best);
+        return best < QN ? best : a_;
+      };
+      float pa[3], na[3], da, sc[PPL];
+      fetch(a_, pa, na, da);
+  #pragma unroll
       for (int s = 0; s < PPL; s++) {
-        const float bp[3] = {pb[0] - cx[s][0], pb[1] - cx[s][1], pb[2] - cx[s][2]};
+        const float dx = pa[0] - cx[s][0], dy = pa[1] - cx[s][1], dz = pa[2] - cx[s][2];
+        sc[s] = cd[s] > 0.0f ? dx * dx + dy * dy + dz * dz : -1e30f;
+      }
+      const int b_ = argmax(sc, MANIFOLD_TOL);
+      float pb[3], nb[3], db;
+      fetch(b_, pb, nb, db);
+      float ab[3];
+      {
+        const float amb[3] = {pa[0] - pb[0], pa[1] - pb[1], pa[2] - pb[2]};
+        cross3(ab, na, amb);
+      }
+  #pragma unroll
+      for (int s = 0; s < PPL; s++) {
         const float ap[3] = {pa[0] - cx[s][0], pa[1] - cx[s][1], pa[2] - cx[s][2]};
-        s1[s] = cd[s] > 0.0f ? fabsf(dot3(bp, bc)) : -1e30f;
-        s2[s] = cd[s] > 0.0f ? fabsf(dot3(ap, ac)) : -1e30f;
-        mx = fmaxf(mx, fmaxf(s1[s], s2[s]));
+        sc[s] = cd[s] > 0.0f ? fabsf(dot3(ap, ab)) : -1e30f;
       }
-      mx = hmax8_nc(mx);
-      int best = 1 << 20;
-#pragma unroll
-      for (int s = PPL - 1; s >= 0; s--) {
-        best = ((cd[s] > 0.0f) & (s2[s] >= mx - MANIFOLD_TOL)) ? QN + sub + 8 * s : best;
+      const int c_ = argmax(sc, MANIFOLD_TOL);
+      float pc[3], nc_[3], dcc;
+      fetch(c_, pc, nc_, dcc);
+      float ac[3], bc[3];
+      {
+        const float amc[3] = {pa[0] - pc[0], pa[1] - pc[1], pa[2] - pc[2]};
+        const float bmc[3] = {pb[0] - pc[0], pb[1] - pc[1], pb[2] - pc[2]};
+        cross3(ac, na, amc);
+        cross3(bc, na, bmc);
       }
-#pragma unroll
-      for (int s = PPL - 1; s >= 0; s--) {
-        best = ((cd[s] > 0.0f) & (s1[s] >= mx - MANIFOLD_TOL)) ? sub + 8 * s : best;
+      int d_;
+      {
+        float s1[PPL], s2[PPL], mx = -1e30f;
+  #pragma unroll
+        for (int s = 0; s < PPL; s++) {
+          const float bp[3] = {pb[0] - cx[s][0], pb[1] - cx[s][1], pb[2] - cx[s][2]};
+          const float ap[3] = {pa[0] - cx[s][0], pa[1] - cx[s][1], pa[2] - cx[s][2]};
+          s1[s] = cd[s] > 0.0f ? fabsf(dot3(bp, bc)) : -1e30f;
+          s2[s] = cd[s] > 0.0f ? fabsf(dot3(ap, ac)) : -1e30f;
+          mx = fmaxf(mx, fmaxf(s1[s], s2[s]));
+        }
+        mx = hmax8_nc(mx);
+        int best = 1 << 20;
+  #pragma unroll
+        for (int s = PPL - 1; s >= 0; s--) {
+          best = ((cd[s] > 0.0f) & (s2[s] >= mx - MANIFOLD_TOL)) ? QN + sub + 8 * s : best;
+        }
+  #pragma unroll
+        for (int s = PPL - 1; s >= 0; s--) {
+          best = ((cd[s] > 0.0f) & (s1[s] >= mx - MANIFOLD_TOL)) ? sub + 8 * s : best;
+        }
+        d_ = hmin8i(best);
+        d_ = d_ < 2 * QN ? (d_ >= QN ? d_ - QN : d_) : a_;
       }
-      d_ = hmin8i(best);
-      d_ = d_ < 2 * QN ? (d_ >= QN ? d_ - QN : d_) : a_;
-    }
-    // slot sub (< 4) of this pair: its contact, repeats inactive (fetches are uniform over the
-    // half-team: a lane's shuffle source selects its slot with the requester's index)
-    float pdd[3], ndd[3], ddd;
-    fetch(d_, pdd, ndd, ddd);
-    // slot sub's contact by v_cndmask on the lanes' sub masks: written as nested ?: on sub, the compiler
-    // made each of the seven values a tree of exec-masked branches
-    const unsigned long long m0 = __ballot(sub == 0), m1 = __ballot(sub == 1), m2 = __ballot(sub == 2);
-    auto pick = [&](float v0, float v1, float v2, float v3) { return vsel(m0, v0, vsel(m1, v1, vsel(m2, v2, v3))); };
-    const int myq = (sub == 0) * a_ + (sub == 1) * b_ + (sub == 2) * c_ + (sub >= 3) * d_;
-    float px[3], pn[3], pd;
-    for (int a = 0; a < 3; a++) {
-      px[a] = pick(pa[a], pb[a], pc[a], pdd[a]);
-      pn[a] = pick(na[a], nb[a], nc_[a], ndd[a]);
-    }
-    pd = pick(da, db, dcc, ddd);
-    if (sub < 4) {
-      const int idx[4] = {a_, b_, c_, d_};
-      bool unique = true;
-      for (int e = 0; e < 4; e++) unique = unique & !((e < sub) & (idx[e] == myq));
-      float fr[9], pw[3], nw[3];
-      if (any) {
-        const float pl[3] = {px[0] + t[0], px[1] + t[1], px[2] + t[2]};
-        mulmv3(pw, PR, pl);
-        for (int a = 0; a < 3; a++) pw[a] += pp[a];
-        mulmv3(nw, PR, pn);
-        make_frame(fr, nw);
-        Ph::store_contact(L, 4 * p + sub, unique ? -pd : 1.0f, pw, fr);
-      } else {
-        const float nofr[9] = {0, 0, 1, 0, 1, 0, -1, 0, 0};
-        const float zero[3] = {L[Ly::COM], L[Ly::COM + 1], L[Ly::COM + 2]};
-        Ph::store_contact(L, 4 * p + sub, 1.0f, zero, nofr);
+      // slot sub (< 4) of this pair: its contact, repeats inactive (fetches are uniform over the
+      // half-team: a lane's shuffle source selects its slot with the requester's index)
+      float pdd[3], ndd[3], ddd;
+      fetch(d_, pdd, ndd, ddd);
+      // slot sub's contact by v_cndmask on the lanes' sub masks: written as nested ?: on sub, the compiler
+      // made each of the seven values a tree of exec-masked branches
+      const unsigned long long m0 = __ballot(sub == 0), m1 = __ballot(sub == 1), m2 = __ballot(sub == 2);
+      auto pick = [&](float v0, float v1, float v2, float v3) { return vsel(m0, v0, vsel(m1, v1, vsel(m2, v2, v3))); };
+      const int myq = (sub == 0) * a_ + (sub == 1) * b_ + (sub == 2) * c_ + (sub >= 3) * d_;
+      float px[3], pn[3], pd;
+      for (int a = 0; a < 3; a++) {
+        px[a] = pick(pa[a], pb[a], pc[a], pdd[a]);
+        pn[a] = pick(na[a], nb[a], nc_[a], ndd[a]);
+      }
+      pd = pick(da, db, dcc, ddd);
+      if (sub < 4) {
+        const int idx[4] = {a_, b_, c_, d_};
+        bool unique = true;
+        for (int e = 0; e < 4; e++) unique = unique & !((e < sub) & (idx[e] == myq));
+        float fr[9], pw[3], nw[3];
+        if (any) {
+          const float pl[3] = {px[0] + t[0], px[1] + t[1], px[2] + t[2]};
+          mulmv3(pw, PR, pl);
+          for (int a = 0; a < 3; a++) pw[a] += pp[a];
+          mulmv3(nw, PR, pn);
+          make_frame(fr, nw);
+          Ph::store_contact(L, 4 * p + sub, unique ? -pd : 1.0f, pw, fr);
+        } else {
+          const float nofr[9] = {0, 0, 1, 0, 1, 0, -1, 0, 0};
+          const float zero[3] = {L[Ly::COM], L[Ly::COM + 1], L[Ly::COM + 2]};
+          Ph::store_contact(L, 4 * p + sub, 1.0f, zero, nofr);
+        }
       }
     }
-#if defined(DUCK_DOUBLE) && DUCK_DOUBLE == 19
-    }
-#endif
-    STAGE_MARK(39);
+    STAGE_MARK(ST_HF_SLOTS);
   }
 
   // Are the boxes enclosing the two hulls (mesh frames p, R) separated? 15-axis box/box SAT
@@ -2879,7 +2774,7 @@ struct TPhys {
     STAGE_T0();
     if constexpr (Md::FLOOR_TYPE == 1) collide_hfield(L, lane, hf);
     else collide_planes(L, lane);
-    STAGE_MARK(26);
+    STAGE_MARK(ST_COLLISION_FLOOR);
     if (Md::FOOT_PAIR >= 0) {
       constexpr int p = Md::FOOT_PAIR;
       const int s1 = cgeom_slot<Md>(Md::pair_geom1[p]), s2 = cgeom_slot<Md>(Md::pair_geom2[p]);
@@ -2902,12 +2797,8 @@ struct TPhys {
         }
       } else {
         TSYNC();
-#ifdef DUCK_STAGE_PROF
-        if (lane == 0) STAGE_ADD(27, 1ull);  // how often the SAT path runs
-#endif
-#ifndef DUCK_DIAG_NO_RARE_CALLS
-        collide_hulls_rare(L, lane);  // rare: the boxes overlap
-#endif
+        STAGE_COUNT_IF(lane == 0, ST_N_FOOT_SAT, 1ull);  // how often the SAT path runs
+        collide_hulls_rare(L, lane);                      // rare: the boxes overlap
       }
     }
     TSYNC();
@@ -3095,9 +2986,7 @@ struct TPhys {
   static DK void solve(LP L, int lane, float* scratch, int stride, const float (*Mc)[NV]) {
     STAGE_T0();
     const float g0 = warm_start(L, lane, Mc);
-#if defined(DUCK_DOUBLE) && DUCK_DOUBLE == 21
-    (void)warm_start(L, lane, Mc);
-#endif
+    STAGE_AGAIN(21, (void)warm_start(L, lane, Mc));
     newton(L, lane, scratch, stride, Mc, g0);
   }
   // latency mode: the warm start's products that need only qacc_warmstart (its feet motions, M and J
@@ -3209,7 +3098,7 @@ struct TPhys {
     float SL[6], SR[6], SL2[6], SR2[6];
     sp_bcast(sw, SL, SR);
     sp_bcast(ss, SL2, SR2);
-    STAGE_MARK(25);
+    STAGE_MARK(ST_WARM_PRODUCTS);
     float cwp = 0.0f, csp = 0.0f, gwp = 0.0f;
     {
       // branchless (no lane-divergent region: see TL::SINK)
@@ -3258,7 +3147,7 @@ struct TPhys {
       g0 = 0.0f;  // gauss(qacc_smooth) = 0.5 (M qs - f).(qs - qs) = 0
     }
     TSYNC();
-    STAGE_MARK(9);
+    STAGE_MARK(ST_WARM_SELECT);
     return g0;
   }
   // Md::iterations Newton steps from the start in QACC / MA / JA (Gauss cost g0 there)
@@ -3277,21 +3166,15 @@ struct TPhys {
       sparse_ok = true;
     } else {
       sparse_ok = newton_fused<false>(L, lane, Mc);
-#if defined(DUCK_DOUBLE) && DUCK_DOUBLE == 22
-      sparse_ok = newton_fused<false>(L, lane, Mc);
-#endif
+      STAGE_AGAIN(22, sparse_ok = newton_fused<false>(L, lane, Mc));
     }
-    STAGE_MARK(10);
+    STAGE_MARK(ST_NEWTON_DIR);
     if (sparse_ok) {
-      STAGE_MARK(11);
+      STAGE_MARK(ST_NEWTON_SPARSE);
     } else {
       TSYNC();
-#ifdef DUCK_STAGE_PROF
-      if (lane == 0) STAGE_ADD(23, 1ull);  // dense Newton fallbacks
-#endif
-#ifndef DUCK_DIAG_NO_RARE_CALLS
+      STAGE_COUNT_IF(lane == 0, ST_N_DENSE_FALLBACK, 1ull);
       newton_dense(L, lane);  // rare: foot/foot contact rows active (dense H)
-#endif
       TSYNC();
     }
     // J.search and M.search in one pass; rows go straight to registers
@@ -3331,14 +3214,7 @@ struct TPhys {
       }
     }
     float sn = 0.0f, sMa = 0.0f, sf = 0.0f, sMv = 0.0f;
-#ifdef DUCK_LS_DUMP
-    {
-      const unsigned long long ex = __builtin_amdgcn_read_exec();
-      L[TL::KC + 88 + lane] = __int_as_float((int)(ex & 0xffffffffull));
-      L[TL::KC + 104 + lane] = __int_as_float((int)(ex >> 32));
-      L[TL::KC + 120 + lane] = L[Ly::SRCH + lane];
-    }
-#endif
+    LS_DUMP_START(L, lane);
     team_for<NV>(lane, [&](int i) {
       const float sv = L[Ly::SRCH + i];
       sn += sv * sv;
@@ -3346,12 +3222,9 @@ struct TPhys {
       sf += sv * L[Ly::FSM + i];
       sMv += sv * L[Ly::GRAD + i];
     });
-#ifdef DUCK_LS_DUMP
-    L[TL::KC + 56 + lane] = (float)lane;
-    L[TL::KC + 72 + lane] = sn;
-#endif
+    LS_DUMP_NORM(L, lane, sn);
     sn = tsum(sn); sMa = tsum(sMa); sf = tsum(sf); sMv = tsum(sMv);
-    STAGE_MARK(12);
+    STAGE_MARK(ST_SEARCH_PRODUCTS);
     const float gtol = Md::tolerance * Md::ls_tolerance * sqrtf(sn) * Md::meaninertia * (float)(NV > 1 ? NV : 1);
     const float G0 = g0, G1 = sMa - sf, G2 = 0.5f * sMv;
     auto mk = [&](float alpha, float q0, float q1, float q2) {
@@ -3370,11 +3243,7 @@ struct TPhys {
     {
       float q0 = 0, q1 = 0, q2 = 0;
       quad2(R, 0.0f, q0, q1, q2);
-#ifdef DUCK_LS_DUMP
-      // debug builds: the line search's inputs, into the (dead) KC scratch of the env slice
-      L[TL::KC + 8 + 3 * lane] = q0; L[TL::KC + 9 + 3 * lane] = q1; L[TL::KC + 10 + 3 * lane] = q2;
-      if (lane == 0) { L[TL::KC] = G0; L[TL::KC + 1] = G1; L[TL::KC + 2] = G2; L[TL::KC + 3] = gtol; L[TL::KC + 4] = sn; }
-#endif
+      LS_DUMP_QUAD(L, lane, q0, q1, q2, G0, G1, G2, gtol, sn);
       p0 = mk(0.0f, q0, q1, q2);
     }
     Pt lo;
@@ -3392,46 +3261,21 @@ struct TPhys {
     // fp32 termination floor: a bracket end whose slope is below 1e-6 of the starting slope is at the
     // minimum to fp32 resolution; MJX's gtol (tolerance * ls_tolerance * |search| ...) alone is far
     // below fp32 noise, so fp32 iterations would keep swapping on rounding
-    const float gtol_ls = fmaxf(gtol, DUCK_LS_DFLOOR * fabsf(p0.d0));
-#ifdef DUCK_LS_NOBREAK
-    bool stop = false;
-#pragma unroll
-    for (int it = 0; it < Md::ls_iterations; it++) {
-      bool done = stop || !swap;
-      done = done || ((lo.d0 < 0.0f) && (lo.d0 > -gtol_ls));
-      done = done || ((hi.d0 > 0.0f) && (hi.d0 < gtol_ls));
-      stop = done;
-#else
-#ifdef DUCK_STAGE_PROF
-    int its = 0;
-#endif
+    const float gtol_ls = fmaxf(gtol, LS_SLOPE_FLOOR * fabsf(p0.d0));
+    STAGE_PROF_ONLY(int its = 0;)  // (iterations this team needed, against those its wave ran)
     for (int it = 0; it < Md::ls_iterations; it++) {
       bool done = !swap;
       done = done || ((lo.d0 < 0.0f) && (lo.d0 > -gtol_ls));
       done = done || ((hi.d0 > 0.0f) && (hi.d0 < gtol_ls));
       if (done) break;
-#ifdef DUCK_STAGE_PROF
-      its = it + 1;
-      if (threadIdx.x < 64 && (int)threadIdx.x == __ffsll((long long)__ballot(1)) - 1) STAGE_ADD(56, 1ull);
-#endif
-#endif
+      STAGE_PROF_ONLY(its = it + 1;)
+      STAGE_COUNT_WAVE0(ST_N_LS_WAVE_ITERS, 1ull);
       const float al = lo.alpha - lo.d0 / lo.d1, ah = hi.alpha - hi.d0 / hi.d1, am = 0.5f * (lo.alpha + hi.alpha);
       float a0 = 0, a1 = 0, a2 = 0, b0 = 0, b1 = 0, b2 = 0, c0 = 0, c1 = 0, c2 = 0;
       quad2(R, al, a0, a1, a2);
       quad2(R, ah, b0, b1, b2);
       quad2(R, am, c0, c1, c2);
       const Pt lo_next = mk(al, a0, a1, a2), hi_next = mk(ah, b0, b1, b2), mid = mk(am, c0, c1, c2);
-#ifdef DUCK_LS_NOBREAK
-      const bool s1 = !done && ((lo.d0 > 0.0f) || (lo.d0 < lo_next.d0));
-      if (s1) lo = lo_next;
-      const bool s2 = !done && (mid.d0 < 0.0f) && (lo.d0 < mid.d0);
-      if (s2) lo = mid;
-      const bool s3 = !done && ((hi.d0 < 0.0f) || (hi.d0 > hi_next.d0));
-      if (s3) hi = hi_next;
-      const bool s4 = !done && (mid.d0 > 0.0f) && (hi.d0 > mid.d0);
-      if (s4) hi = mid;
-      swap = done ? swap : (s1 || s2 || s3 || s4);
-#else
       const bool s1 = (lo.d0 > 0.0f) || (lo.d0 < lo_next.d0);
       if (s1) lo = lo_next;
       const bool s2 = (mid.d0 < 0.0f) && (lo.d0 < mid.d0);
@@ -3441,18 +3285,18 @@ struct TPhys {
       const bool s4 = (mid.d0 > 0.0f) && (hi.d0 > mid.d0);
       if (s4) hi = mid;
       swap = s1 || s2 || s3 || s4;
-#endif
     }
-#if defined(DUCK_STAGE_PROF) && !defined(DUCK_LS_NOBREAK)
-    if (threadIdx.x < 64 && (lane & 15) == 0) { STAGE_ADD(57, (unsigned long long)its); STAGE_ADD(58, 1ull); }
-#endif
+    STAGE_PROF_ONLY(if (threadIdx.x < 64 && (lane & 15) == 0) {
+      STAGE_COUNT(ST_N_LS_TEAM_ITERS, (unsigned long long)its);
+      STAGE_COUNT(ST_N_LS_SEARCHES, 1ull);
+    })
     const float lo_cost = cost(lo), hi_cost = cost(hi), p0_cost = cost(p0);
     const bool improved = (lo_cost < p0_cost) || (hi_cost < p0_cost);
     const float alpha = lo_cost < hi_cost ? lo.alpha : hi.alpha;
     if (improved)
       team_for<NV>(lane, [&](int i) { L[Ly::QACC + i] += L[Ly::SRCH + i] * alpha; });
     TSYNC();
-    STAGE_MARK(13);
+    STAGE_MARK(ST_LINESEARCH);
     if constexpr (Md::iterations <= 1) {
       break;
     } else {
@@ -3580,59 +3424,39 @@ struct TPhys {
                       int sstride, const float* hf) {
     STAGE_T0();
     kinematics(L, lane);
-#if defined(DUCK_DOUBLE) && DUCK_DOUBLE == 6
-    kinematics(L, lane);
-#endif
-    STAGE_MARK(0);
+    STAGE_AGAIN(6, kinematics(L, lane));
+    STAGE_MARK(ST_KINEMATICS);
     com_pos(L, lane);
-#if defined(DUCK_DOUBLE) && DUCK_DOUBLE == 7
-    com_pos(L, lane);
-#endif
-    STAGE_MARK(1);
+    STAGE_AGAIN(7, com_pos(L, lane));
+    STAGE_MARK(ST_COM_POS);
     rne(L, lane);
-    STAGE_MARK(2);
+    STAGE_MARK(ST_RNE);
     crb(L, lane);
-    // DUCK_DOUBLE (measurement builds, tools/gpu_stage_double.sh, tools/gpu_stage_pmc.sh): one
-    // idempotent stage runs twice, and the launch-time (and counter) difference to the normal build
-    // is that stage's cost, unperturbed by markers: 1 crb, 2 collision, 3 make_rows, 4 smooth_acc,
-    // 5 solve, 6 kinematics, 7 com_pos, 8 rne + smooth (height field: 11-20, tools/stage_pmc_summary.py)
-#if defined(DUCK_DOUBLE) && DUCK_DOUBLE == 1
-    crb(L, lane);
-#endif
-    STAGE_MARK(3);
+    STAGE_AGAIN(1, crb(L, lane));
+    STAGE_MARK(ST_CRB);
     smooth(L, lane);
-#if defined(DUCK_DOUBLE) && DUCK_DOUBLE == 8
-    rne(L, lane);  // (smooth adds to rne's qfrc_smooth: the pair is idempotent, smooth alone is not)
-    smooth(L, lane);
-#endif
-    STAGE_MARK(28);
+    STAGE_AGAIN(8, rne(L, lane));  // (smooth adds to rne's qfrc_smooth: the pair is idempotent, smooth alone is not)
+    STAGE_AGAIN(8, smooth(L, lane));
+    STAGE_MARK(ST_SMOOTH);
     // collision and the constraint rows depend on the kinematics only: they run before the
     // smooth acceleration so that M is loaded into registers once for both solves
     collision(L, lane, hf);
-#if defined(DUCK_DOUBLE) && DUCK_DOUBLE == 2
-    collision(L, lane, hf);
-#endif
-    STAGE_MARK(5);
+    STAGE_AGAIN(2, collision(L, lane, hf));
+    STAGE_MARK(ST_COLLISION);
     make_rows(L, lane);
-#if defined(DUCK_DOUBLE) && DUCK_DOUBLE == 3
-    make_rows(L, lane);
-#endif
-    STAGE_MARK(6);
+    STAGE_AGAIN(3, make_rows(L, lane));
+    STAGE_MARK(ST_MAKE_ROWS);
     {
       float Mc[NC][NV];
       load_cols(L, lane, Mc, false);
-      STAGE_MARK(20);
+      STAGE_MARK(ST_LOAD_COLS);
       smooth_acc(L, lane, Mc);
-#if defined(DUCK_DOUBLE) && DUCK_DOUBLE == 4
-      smooth_acc(L, lane, Mc);
-#endif
-      STAGE_MARK(4);
+      STAGE_AGAIN(4, smooth_acc(L, lane, Mc));
+      STAGE_MARK(ST_SMOOTH_ACC);
       solve(L, lane, scratch, sstride, Mc);
-#if defined(DUCK_DOUBLE) && DUCK_DOUBLE == 5
-      solve(L, lane, scratch, sstride, Mc);  // (reads qacc_warmstart / qacc_smooth, not qacc)
-#endif
+      STAGE_AGAIN(5, solve(L, lane, scratch, sstride, Mc));  // (reads qacc_warmstart / qacc_smooth, not qacc)
     }
-    STAGE_MARK(7);
+    STAGE_MARK(ST_SOLVE);
     if (want_out) {
       sensors(L, lane);
       if (aux) {
@@ -3645,7 +3469,7 @@ struct TPhys {
       team_for<NV>(lane, [&](int i) { L[Ly::WARM + i] = L[Ly::QACC + i]; });
       TSYNC();
     }
-    STAGE_MARK(8);
+    STAGE_MARK(ST_SENSORS_EULER);
   }
 
   // ---------------- latency mode: one substep over three waves (step_kernel_lat) ----------------

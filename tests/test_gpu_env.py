@@ -293,6 +293,49 @@ def test_latency_timeout_surfaces(mode, wg_envs, gpu, monkeypatch):
     env.reset(rng=2)                         # usable again once cleared
 
 
+def test_stage_profile_build_counts(gpu, monkeypatch):
+    """The stage-profile build (native.debug_library "stage_prof", -DDUCK_STAGE_PROF) after 2 env-steps of
+    17 envs in the throughput kernel (two workgroups, the second partial): duck_debug_stage_cycles fills
+    exactly DUCK_STAGE_CYCLES_WORDS words (the guard words after them stay), every top-level stage has
+    counted cycles, and no latency wait gave up. The shipped library answers DUCK_EUNSUPPORTED and writes
+    nothing."""
+    import ctypes as C
+    import os
+    import sys
+    from open_duck_playground_amd import joystick as jmod
+    from open_duck_playground_amd.cabi import STAGE_CYCLES_WORDS
+    from open_duck_playground_amd.native import BUILD
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    import stage_table
+    path = os.path.join(BUILD, "libduck_stage_prof.so")
+    assert os.path.exists(path), "built by __graft_entry__.build()"
+    GUARD, NG, n = 0xA5A5A5A5A5A5A5A5, 64, 17
+
+    def run(env):
+        env.set_step_mode("throughput")
+        st = env.reset(rng=1)
+        for _ in range(2):
+            st = env.step(st, torch.zeros(n, 14, device=gpu))
+        torch.cuda.synchronize()
+        buf = (C.c_ulonglong * (STAGE_CYCLES_WORDS + NG))(*([GUARD] * (STAGE_CYCLES_WORDS + NG)))
+        rc = env._lib.duck_debug_stage_cycles(env._sim, buf, 0)
+        return rc, list(buf)
+
+    rc, buf = run(Joystick("flat_terrain", num_envs=n, device=gpu, use_imitation=False))
+    assert rc == -2 and all(v == GUARD for v in buf)  # DUCK_EUNSUPPORTED
+    monkeypatch.setattr(jmod, "model_library", lambda m: path)
+    env = Joystick("flat_terrain", num_envs=n, device=gpu, use_imitation=False)
+    rc, buf = run(env)
+    assert rc == 0
+    assert all(v == GUARD for v in buf[STAGE_CYCLES_WORDS:])
+    top = ["KINEMATICS", "COM_POS", "RNE", "CRB", "SMOOTH", "COLLISION", "MAKE_ROWS", "LOAD_COLS", "SMOOTH_ACC", "SOLVE",
+           "SENSORS_EULER"]
+    zero = [t for t in top if buf[stage_table.NUM[t]] == 0]
+    print({t: buf[stage_table.NUM[t]] for t in top})
+    assert not zero, zero
+    assert env.lat_timeouts() == 0
+
+
 def test_step_mode_auto_selects_by_batch(gpu):
     """AUTO: the latency kernel while the batch leaves a CU per 4 envs, the paired latency kernel while
     it leaves a CU per 8, the throughput kernel above."""

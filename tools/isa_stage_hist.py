@@ -1,12 +1,11 @@
 #!/usr/bin/env python3
 """Static instruction mix of the step kernel per stage (CPU only).
 
-Compiles one scene unit to assembly with -DDUCK_ASM_MARKS (each STAGE_MARK(k) becomes the comment
-"; STAGE_MARK k", no code) and the library's own flags, then counts the instructions of
-step_kernel<...> between consecutive marks: the region that ends at mark k is named after k
-(duck_team.h: 0 kinematics, 1 com_pos, 2 rne, 3 crb, 28 smooth, 5 collision, 6 make_rows, 20 load_cols,
-4 smooth_acc, 25/9 warm start, 16-18 Newton direction, 12 search products, 13 line search, 7/8
-sensors + Euler). Static counts of straight-line code are its per-substep dynamic counts; loops
+Compiles one scene unit to assembly with -DDUCK_ASM_MARKS (each STAGE_MARK(ST_x) becomes the comment
+"; STAGE_MARK ST_x", no code) and the library's own flags, then counts the instructions of
+step_kernel<...> between consecutive marks: the region that ends at mark x carries x's number and
+label (csrc/duck_measure.h's stage table, stage_table.py). Static counts of straight-line code are
+its per-substep dynamic counts; loops
 (the line search, the height field's queue) run more often.
 
 usage: python tools/isa_stage_hist.py [--variant flat] [--kernel step_kernel] [--lat 0]
@@ -20,12 +19,8 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = {0: "kinematics", 1: "com_pos", 2: "rne", 3: "crb", 28: "smooth", 5: "collision", 6: "make_rows",
-         20: "load_cols", 4: "smooth_acc", 25: "warm start (products)", 9: "warm start (rows, choice)",
-         16: "newton: gradient + M columns", 17: "newton: J'DJ blocks", 18: "newton: factor + solves",
-         10: "newton: store", 11: "newton: -", 12: "search products + rows", 13: "line search + update",
-         7: "solve tail", 8: "sensors + euler", 24: "kinematics (poses)", 21: "rne: velocities",
-         22: "rne: forces", 35: "rne: subtree a", 36: "rne: subtree b", 19: "crb: inertias", 26: "collision: planes"}
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import stage_table as T  # noqa: E402
 
 
 def classify(op):
@@ -84,10 +79,10 @@ def main():
     body = m.group(2)
     regions, cur, order = collections.OrderedDict(), collections.Counter(), []
     for line in body.splitlines():
-        mk = re.match(r"\s*;\s*STAGE_MARK (\d+)", line)
+        mk = re.match(r"\s*;\s*STAGE_MARK ST_(\w+)", line)
         if mk:
-            k = int(mk.group(1))
-            key = f"{k:>2} {NAMES.get(k, '?')}"
+            k = T.NUM[mk.group(1)]
+            key = f"{k:>2} {T.LABEL[k]}"
             regions.setdefault(key, collections.Counter()).update(cur)
             cur = collections.Counter()
             continue

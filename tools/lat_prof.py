@@ -13,6 +13,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+import stage_table as T  # noqa: E402
 from bench import CONFIGS  # noqa: E402
 from open_duck_playground_amd.joystick import Joystick, domain_randomize, wrap_for_brax_training  # noqa: E402
 
@@ -34,7 +35,8 @@ NAMES2 = {0: "A start (Euler of s-1 seen)", 1: "A kinematics+com_pos done", 2: "
           20: "B direction seen / own", 21: "B Newton + line search done", 22: "B Euler done"}
 LAUNCH = {40: "kernel start", 41: "model blob in LDS", 42: "hot state staged", 43: "w0 env code before the substeps done",
           44: "w0 last Euler seen", 45: "w0 env code after the substeps done", 46: "final barrier"}
-NSTAGE = 56
+# (NAMES, NAMES2, LAUNCH: the latency kernels' event slots, LAT_T(k, s); the stage counters are stage_table's)
+NSTAGE = T.NSTAGE
 
 
 def main():
@@ -52,7 +54,7 @@ def main():
     st = env.reset(rng=0)
     g = torch.Generator(device=dev)
     g.manual_seed(1)
-    buf = (C.c_ulonglong * (NSTAGE + 3 * 1024))()
+    buf = (C.c_ulonglong * T.CYCLES_WORDS)()
     rows = []
     stage = np.zeros(64)
     nl = 0
@@ -78,8 +80,7 @@ def main():
         print(f"{r[k]:9.0f}  {names[k]}")
     print(f"substep (start -> Euler): {r[last]:.0f} cycles")
     # per-stage cycles (STAGE_MARK sums, workgroup 0), per substep
-    from stage_prof import ENV, SUB, TOP  # noqa: E402
-    names = {**TOP, **SUB, **ENV}
+    names = T.LABEL
     per = stage / max(nl, 1) / env.n_substeps
     print("stage cycles per substep (marks from each stage function's start):")
     for k in np.argsort(-per):

@@ -17,11 +17,10 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STAGES = {1: "crb", 2: "collision", 3: "make_rows", 4: "smooth_acc (qacc_smooth factor + solves)",
-          5: "solve (warm start + Newton + line search)", 6: "kinematics", 7: "com_pos", 8: "rne + smooth",
-          11: "hf SAT pass 2", 12: "hf SAT pass 1", 13: "hf contact point", 14: "hf screen",
-          15: "hf vertical-edge pairs", 16: "hf setup (frames, hull vertices, box, sub-grid, side minima)",
-          17: "hf silhouette lists", 18: "hf survivor descriptors", 19: "hf manifold slots + contact stores", 20: "hf hull-face axes", 21: "warm start", 22: "Newton direction (gradient, J'DJ, factor + solves)"}
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import stage_table as T  # noqa: E402
+
+STAGES = dict(T.DOUBLES)  # DUCK_DOUBLE = k (csrc/duck_measure.h)
 
 
 def build(variant, stages):

@@ -2,32 +2,33 @@
 """Per-stage cycle breakdown of step_kernel (needs a -DDUCK_STAGE_PROF build in DUCK_LIB).
 
 Counters are wave-0 clock64 deltas summed over workgroups; printed per substep per wave.
-Top-level stages (they partition a substep): 0-8, 20 and 28. Sub-stage counters measure from
-the start of their parent stage: 9-13 solve, 16-18 newton direction, 19 crb limb/root
-sums, 21/22 rne passes A/B, 24 kinematics local transforms, 26 floor collision.
+The top-level stages (TOP) partition a substep. Sub-stage counters (SUB) measure from the start of
+their parent stage. Numbers and labels come from csrc/duck_measure.h (stage_table.py).
 """
 import ctypes as C
 import os
 import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch  # noqa: E402
 
 from open_duck_playground_amd import native  # noqa: E402
 from open_duck_playground_amd.joystick import Joystick, wrap_for_brax_training  # noqa: E402
 
-TOP = {0: "kinematics", 1: "com_pos", 2: "rne", 3: "crb", 28: "smooth (actuation, damping)",
-       5: "collision", 6: "make_rows", 20: "M columns -> registers", 4: "qacc_smooth solve", 7: "solve",
-       8: "sensors+euler"}
-SUB = {24: "kinematics:local", 21: "rne:A vel/acc", 22: "rne:A+B forces", 35: "rne:C limb sums", 36: "rne:C root sums", 19: "crb:inertia sums",
-       26: "collision:floor", 25: "solve:warm J,M products", 9: "solve:warm costs+select", 10: "solve:newton_dir", 16: "  newton:grad+diag",
-       17: "  newton:+J'DJ", 18: "  newton:+factor_solve", 11: "solve:(dense fallback)", 12: "solve:jmul+mulM",
-       13: "solve:linesearch", 37: "hfield: setup+screen+silhouettes", 38: "hfield: survivor queue", 39: "hfield: slots",
-       41: "  queue: descriptors", 42: "  queue: per-lane SAT", 43: "  queue: gather",
-       44: "    sat: vertical pairs", 45: "    sat: pass 1 (arc tests)", 47: "    sat: pass 2 (crossing pairs)"}
-NSTAGE = 60  # DUCK_NSTAGE
-ENV = {32: "env: hot state load", 33: "env: rng draws", 29: "env: pre-physics (per env-step)", 30: "env: contacts+obs",
-       31: "env: termination+rewards+state", 34: "env: obs/priv stores", 15: "env: hot state store"}
+import stage_table as T  # noqa: E402
+
+# how this tool groups the stages (numbers and labels: csrc/duck_measure.h); "  " indents a sub-stage
+_group = lambda ids: {T.NUM[i.strip()]: i[:len(i) - len(i.lstrip())] + T.LABEL[T.NUM[i.strip()]] for i in ids}
+TOP = _group(["KINEMATICS", "COM_POS", "RNE", "CRB", "SMOOTH", "COLLISION", "MAKE_ROWS", "LOAD_COLS", "SMOOTH_ACC", "SOLVE",
+              "SENSORS_EULER"])
+SUB = _group(["KIN_LOCAL", "RNE_A", "RNE_B", "RNE_LIMB", "RNE_ROOT", "CRB_SUMS", "COLLISION_FLOOR", "WARM_PRODUCTS",
+              "WARM_SELECT", "NEWTON_DIR", "  NEWTON_GRAD", "  NEWTON_JDJ", "  NEWTON_FACTOR", "NEWTON_SPARSE",
+              "SEARCH_PRODUCTS", "LINESEARCH", "HF_SCREEN", "HF_QUEUE", "HF_SLOTS", "  HFQ_DESC", "  HFQ_SAT", "  HFQ_GATHER",
+              "    SAT_VERTICAL", "    SAT_PASS1", "    SAT_PASS2"])
+ENV = _group(["ENV_HOT_LOAD", "ENV_RNG", "ENV_PRE", "ENV_CONTACTS_OBS", "ENV_TERM", "ENV_OBS_STORE", "ENV_HOT_STORE"])
+NSTAGE = T.NSTAGE
+N = T.NUM
 
 
 def main():
@@ -45,7 +46,7 @@ def main():
     for i in range(warm):
         st = env.step(st, pool[i % len(pool)], inplace=True)
     torch.cuda.synchronize()
-    buf = (C.c_ulonglong * (NSTAGE + 3 * 1024))()
+    buf = (C.c_ulonglong * T.CYCLES_WORDS)()
     lib = native.lib()
     lib.duck_debug_stage_cycles(env._sim, buf, 1)
     steps = next((int(a.split("=", 1)[1]) for a in sys.argv if a.startswith("--steps=")), 5)
@@ -85,30 +86,31 @@ def main():
                       f"end {us(t1[x::8]).mean():7.1f} {us(t1[x::8]).max():7.1f}  "
                       f"duration mean {((t1[x::8] - t0[x::8]) / 100).mean():7.1f}")
             print(f"  launch span (first start to last end): {us(t1).max():.1f} us")
-    print(f"{'dense Newton fallbacks':28s} {buf[23] / steps:10.1f} per env-step (all {n} envs)")
-    print(f"{'foot/foot SAT runs':28s} {buf[27] / steps:10.1f} per env-step (all {n} envs)")
-    if buf[40]:
-        print(f"{'hfield survivors':28s} {buf[40] / (nwg * steps * 10):10.2f} per substep (wave 0 of each workgroup: 8 feet)")
-        print(f"{'hfield queue rounds':28s} {buf[46] / (nwg * steps * 10):10.2f} per substep (wave 0)")
-        print(f"{'hfield pass-2 iterations':28s} {buf[48] / (nwg * steps * 10):10.2f} per substep (wave 0: the most crossing pairs of a lane)")
-        print(f"{'hfield crossing pairs':28s} {buf[49] / (nwg * steps * 10):10.2f} per substep (wave 0: all survivors)")
-        print(f"{'hfield crossing edges':28s} {buf[50] / (nwg * steps * 10):10.2f} per substep (wave 0: hull edges crossing in any survivor)")
-        hist = [buf[k] for k in range(51, 56)]
+    print(f"{'dense Newton fallbacks':28s} {buf[N['N_DENSE_FALLBACK']] / steps:10.1f} per env-step (all {n} envs)")
+    print(f"{'foot/foot SAT runs':28s} {buf[N['N_FOOT_SAT']] / steps:10.1f} per env-step (all {n} envs)")
+    if buf[N['N_HF_SURVIVORS']]:
+        print(f"{'hfield survivors':28s} {buf[N['N_HF_SURVIVORS']] / (nwg * steps * 10):10.2f} per substep (wave 0 of each workgroup: 8 feet)")
+        print(f"{'hfield queue rounds':28s} {buf[N['N_HF_ROUNDS']] / (nwg * steps * 10):10.2f} per substep (wave 0)")
+        print(f"{'hfield pass-2 iterations':28s} {buf[N['N_HF_PASS2_ITERS']] / (nwg * steps * 10):10.2f} per substep (wave 0: the most crossing pairs of a lane)")
+        print(f"{'hfield crossing pairs':28s} {buf[N['N_HF_PAIRS']] / (nwg * steps * 10):10.2f} per substep (wave 0: all survivors)")
+        print(f"{'hfield crossing edges':28s} {buf[N['N_HF_EDGES']] / (nwg * steps * 10):10.2f} per substep (wave 0: hull edges crossing in any survivor)")
+        hist = [buf[N['N_HF_SURV_LE21']], buf[N['N_HF_SURV_LE32']], buf[N['N_HF_SURV_LE42']], buf[N['N_HF_SURV_LE64']],
+                buf[N['N_HF_SURV_GT64']]]
         if sum(hist):
             print(f"{'hfield survivors per wave':28s} " + ", ".join(
                 f"{lab}: {100 * v / sum(hist):.1f} %" for lab, v in zip(("<=21", "22-32", "33-42", "43-64", ">64"), hist)))
-    outside = per(14) + sum(per(k) for k in ENV)
+    outside = per(N['MODEL_COPY']) + sum(per(k) for k in ENV)
     kern = outside + tot / (nwg * steps)
-    if per(14) == 0:
+    if per(N['MODEL_COPY']) == 0:
         return
-    if buf[58] > 0:
+    if buf[N['N_LS_SEARCHES']] > 0:
         # line search (wave 0 of each workgroup): iterations the wave ran vs its teams needed
-        print(f"{'line search iterations':28s} per team {buf[57] / buf[58]:.2f}, per wave {4 * buf[56] / buf[58]:.2f} "
-              f"({buf[58] / (nwg * steps * 10) / 4:.2f} searches per team and substep)")
+        print(f"{'line search iterations':28s} per team {buf[N['N_LS_TEAM_ITERS']] / buf[N['N_LS_SEARCHES']]:.2f}, per wave {4 * buf[N['N_LS_WAVE_ITERS']] / buf[N['N_LS_SEARCHES']]:.2f} "
+              f"({buf[N['N_LS_SEARCHES']] / (nwg * steps * 10) / 4:.2f} searches per team and substep)")
     print(f"{'kernel (per env-step)':28s} {kern:10.0f} cycles/env-step/wave (sum of the marked sections)")
-    print(f"{'  model-table copy':28s} {per(14):10.0f}  {100 * per(14) / kern:5.1f}%")
+    print(f"{'  model-table copy':28s} {per(N['MODEL_COPY']):10.0f}  {100 * per(N['MODEL_COPY']) / kern:5.1f}%")
     print(f"{'  10 substeps':28s} {tot / (nwg * steps):10.0f}  {100 * tot / (nwg * steps) / kern:5.1f}%")
-    print(f"{'  env code outside':28s} {outside - per(14):10.0f}  {100 * (outside - per(14)) / kern:5.1f}%")
+    print(f"{'  env code outside':28s} {outside - per(N['MODEL_COPY']):10.0f}  {100 * (outside - per(N['MODEL_COPY'])) / kern:5.1f}%")
 
 
 if __name__ == "__main__":
