@@ -349,6 +349,45 @@ def test_clip_adam_matches_torch(gpu):
         assert err <= 1e-6, (scale, err)
 
 
+@pytest.mark.parametrize("P", [1, 2047, 2048, 2049, 526_337])
+def test_clip_adam_matches_torch_sizes(gpu, P):
+    """test_clip_adam_matches_torch at the sizes where the launch geometry changes: one entry, one workgroup
+    (2048 entries) less one / exactly / plus one, and 257 workgroups, where the update's strided sum of the
+    norm partials (thread t: partials t, t + 256, ..) makes a second trip. The same comparison and 1e-6, and
+    the first moment against torch's to 1e-5 of its largest entry; two steps for the large size."""
+    from open_duck_playground_amd.native import check, lib
+    L = lib()
+    torch.manual_seed(4 + P)
+    assert L.duck_clip_adam_scratch_size(P) == -(-P // 2048)
+    p0 = torch.randn(P, device=gpu)
+    steps = 2 if P > 100_000 else 5
+    for scale, max_norm in ((10.0, 1.0), (1e-4, 1.0)):
+        ref = torch.nn.Parameter(p0.clone())
+        opt = torch.optim.Adam([ref], lr=3e-4)
+        p = p0.clone()
+        m, v = torch.zeros(P, device=gpu), torch.zeros(P, device=gpu)
+        step = torch.zeros(1, dtype=torch.int32, device=gpu)
+        scratch = torch.zeros(L.duck_clip_adam_scratch_size(P), device=gpu)
+        for _ in range(steps):
+            g = scale * torch.randn(P, device=gpu)
+            ref.grad = g.clone()
+            torch.nn.utils.clip_grad_norm_([ref], max_norm)
+            opt.step()
+            check(L.duck_clip_adam(P, p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), scratch.data_ptr(),
+                                   step.data_ptr(), 3e-4, 0.9, 0.999, 1e-8, max_norm,
+                                   torch.cuda.current_stream().cuda_stream))
+        torch.cuda.synchronize()
+        assert int(step.item()) == steps
+        err = float((p - ref.detach()).abs().max())
+        assert err <= 1e-6, (scale, err)
+        # Adam's step is invariant to the gradient's scale, so the parameters hardly see a wrong clip norm; the
+        # first moment is linear in it. fp32 sums of the squares agree to ~1e-6; a norm partial left out of
+        # 257 is 2e-3.
+        m_ref = opt.state[ref]["exp_avg"]
+        err = float((m - m_ref).abs().max()) / float(m_ref.abs().max())
+        assert err <= 1e-5, (scale, err)
+
+
 def test_clip_adam_reduce_equals_reduce_then_clip_adam(gpu):
     """duck_clip_adam_reduce (the weight-gradient partials summed by the update's first launch, one rank)
     gives the same bits as duck_mlp_wgrad_reduce + duck_clip_adam: gradient, moments, parameters, step."""
