@@ -137,6 +137,33 @@ int duck_mlp_wgrad_reduce(int P, int splits, const float* partial, float* grad, 
  * captured graph draws fresh noise on every replay). A <= 16. */
 int duck_policy_sample(int N, int A, const float* logits, unsigned long long seed, unsigned int* ctr, float* raw,
                        float* logprob, float* action, void* stream);
+/* The evaluator's deterministic policy in ONE launch (csrc/duck_policy.hip): the hidden activations stay in
+ * LDS, a workgroup takes 16 rows through every layer.
+ * obs [N][sizes[0]] -> (obs - mean) * istd (both NULL: plain) -> nlayers Dense layers, SiLU between them
+ * (nn.Linear layout, W[l] [sizes[l+1]][sizes[l]], b[l] [sizes[l+1]]) -> logits [N][sizes[nlayers]] = (loc | pre-scale),
+ * action [N][A] = tanh(loc), A = sizes[nlayers] / 2 (brax NormalTanhDistribution.mode; ppo.NormalTanh.mode).
+ * sizes, W and b are HOST arrays (copied into the launch's arguments); everything they point to is device memory.
+ * logits may be NULL. 1 <= nlayers <= DUCK_POLICY_MAX_LAYERS, every size in 1..512, last size even; else DUCK_EINVAL.
+ * The logits are bit-identical to the rollout's chain of duck_mlp_gemm (mode 1 per hidden layer, then mode 0):
+ * the same fp32 MFMA reduction order per output element, the same normaliser, bias and SiLU expressions. */
+#define DUCK_POLICY_MAX_LAYERS 4
+int duck_policy_act(int N, int nlayers, const int* sizes, const float* const* W, const float* const* b,
+                    const float* mean, const float* istd, const float* obs, float* logits, float* action, void* stream);
+
+/* Episode bookkeeping around an env-step (brax EvalWrapper / EpisodeWrapper), one launch per env-step.
+ * F = nmetrics + 2 columns per env: 0 = reward, 1..nmetrics = metrics[k][e] (row k at metrics + k * metrics_stride:
+ * the fstate SoA rows, stride = num_envs), F - 1 = steps.  run, fin: [n][F] row-major float32; flag [n] float32.
+ * EVAL  (brax EvalWrapper; ppo.evaluate): flag = active (caller sets 1). If active: run[e][c] += x[c],
+ *        run[e][F-1] += 1; then active = 0 where done != 0. An inactive env adds nothing. fin unused (may be NULL).
+ * TRAIN (brax EpisodeWrapper's episode_metrics): run[e][c] += x[c], run[e][F-1] += 1; where done != 0:
+ *        fin[e][c] += run[e][c] for every c, flag[e] += 1 (episodes finished), run[e][.] = 0.
+ * Plain fp32 adds in step order (a torch restatement reproduces the accumulators bit for bit); means and
+ * standard deviations over envs come from duck_column_stats(n, F, run | fin, ...). Defined in csrc/duck_capi.hip:
+ * it reads the step kernel's outputs and ships with every model's library. */
+enum { DUCK_EPISODE_EVAL = 0, DUCK_EPISODE_TRAIN = 1 };
+int duck_episode_accumulate(int n, int nmetrics, const float* reward, const float* done, const float* metrics,
+                            int metrics_stride, int mode, float* run, float* fin, float* flag, void* stream);
+
 /* The learner's parameter update on flat buffers of P floats (both networks): clip_grad_norm_(max_norm)
  * then Adam (torch.optim.Adam / optax.adam): g' = g min(1, max_norm / (|g| + 1e-6)),
  * m = b1 m + (1 - b1) g', v = b2 v + (1 - b2) g'^2, t = ++*step,

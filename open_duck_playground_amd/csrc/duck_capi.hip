@@ -3,6 +3,7 @@
 // variant (variant_*.hip). Every entry returns DUCK_OK or a negative code with a
 // thread-local message; no entry allocates, synchronises or throws on the step path.
 #include "duck_common.h"
+#include "../../include/duck_ppo.h"
 
 // the compiled model variants of this library (codegen.variant_registry; generated/ for libduck.so,
 // a per-model build directory for a library compiled for another model, native.model_library)
@@ -52,9 +53,59 @@ struct Fnv {
     for (int i = 0; i < n; i++) { float v = a ? (float)a[i] : 0.0f; bytes(&v, 4); }
   }
 };
+
+// The episode bookkeeping brax wraps around an env (include/duck_ppo.h: duck_episode_accumulate), one thread
+// per env over its F = nmetrics + 2 accumulator columns: plain fp32 adds in step order. It reads the step
+// kernel's outputs (reward, done, the metrics rows of the SoA state), so it lives in this unit and ships
+// with every model's library.
+__global__ __launch_bounds__(256) void episode_accumulate_kernel(int n, int nmetrics, const float* __restrict__ reward,
+                                                                 const float* __restrict__ done,
+                                                                 const float* __restrict__ metrics, int stride,
+                                                                 int mode, float* __restrict__ run,
+                                                                 float* __restrict__ fin, float* __restrict__ flag) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= n) return;
+  const int F = nmetrics + 2;
+  float* r = run + (size_t)e * F;
+  const bool d = done[e] != 0.f;
+  if (mode == DUCK_EPISODE_EVAL) {
+    if (flag[e] == 0.f) return;
+    r[0] += reward[e];
+    for (int k = 0; k < nmetrics; k++) r[1 + k] += metrics[(size_t)k * stride + e];
+    r[F - 1] += 1.f;
+    if (d) flag[e] = 0.f;
+    return;
+  }
+  r[0] += reward[e];
+  for (int k = 0; k < nmetrics; k++) r[1 + k] += metrics[(size_t)k * stride + e];
+  r[F - 1] += 1.f;
+  if (d) {
+    float* f = fin + (size_t)e * F;
+    for (int c = 0; c < F; c++) {
+      f[c] += r[c];
+      r[c] = 0.f;
+    }
+    flag[e] += 1.f;
+  }
+}
 }  // namespace
 
 extern "C" {
+
+int duck_episode_accumulate(int n, int nmetrics, const float* reward, const float* done, const float* metrics,
+                            int metrics_stride, int mode, float* run, float* fin, float* flag, void* stream) {
+  if (n < 0 || nmetrics < 0 || (nmetrics > 0 && metrics_stride < n))
+    return duck_fail(DUCK_EINVAL, "duck_episode_accumulate: bad size");
+  if (mode != DUCK_EPISODE_EVAL && mode != DUCK_EPISODE_TRAIN)
+    return duck_fail(DUCK_EINVAL, "duck_episode_accumulate: mode must be DUCK_EPISODE_EVAL or DUCK_EPISODE_TRAIN");
+  if (n == 0) return DUCK_OK;
+  if (!reward || !done || (nmetrics > 0 && !metrics) || !run || !flag || (mode == DUCK_EPISODE_TRAIN && !fin))
+    return duck_fail(DUCK_EINVAL, "duck_episode_accumulate: null pointer");
+  hipLaunchKernelGGL(episode_accumulate_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, nmetrics,
+                     reward, done, metrics, metrics_stride, mode, run, fin, flag);
+  HIPCHECK(hipGetLastError());
+  return DUCK_OK;
+}
 
 uint64_t duck_model_fingerprint(const duck_model_desc* m) {
   if (!m) return 0;

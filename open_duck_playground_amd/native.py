@@ -27,7 +27,7 @@ EXPORTS = ["duck_version", "duck_build_id", "duck_last_error", "duck_layout_get"
            "duck_step_kernel_for", "duck_debug_lat_timeouts", "duck_gather_columns", "duck_mlp_group",
            "duck_device_error", "duck_gae_stats", "duck_ppo_loss_stats", "duck_mlp_group_bn", "duck_gather_columns_norm",
            "duck_column_stats", "duck_column_stats_scratch", "duck_clip_adam_reduce", "duck_ppo_loss_grad",
-           "duck_ppo_loss_sums", "duck_mlp_group_tiles"]
+           "duck_ppo_loss_sums", "duck_mlp_group_tiles", "duck_policy_act", "duck_episode_accumulate"]
 
 
 class DuckMlpProblem(C.Structure):
@@ -312,6 +312,8 @@ def lib(path: str = None):
         if hasattr(L, "duck_column_stats"):
             L.duck_column_stats.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp]
             L.duck_column_stats_scratch.argtypes = [C.c_int, C.c_int]
+        if hasattr(L, "duck_episode_accumulate"):
+            L.duck_episode_accumulate.argtypes = [C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
         if hasattr(L, "duck_gather_columns"):
             L.duck_gather_columns.argtypes = [C.c_int, C.POINTER(DuckGatherField), vp, C.c_int, vp]
         if hasattr(L, "duck_mlp_gemm"):
@@ -320,6 +322,8 @@ def lib(path: str = None):
             L.duck_mlp_wgrad.argtypes = [ci, ci, ci, vp, vp, vp, vp, ci, vp, ci, ci, ci, vp]
             L.duck_mlp_wgrad_reduce.argtypes = [ci, ci, vp, vp, vp]
             L.duck_policy_sample.argtypes = [ci, ci, vp, C.c_uint64, vp, vp, vp, vp, vp]
+            if hasattr(L, "duck_policy_act"):
+                L.duck_policy_act.argtypes = [ci, ci, C.POINTER(ci), C.POINTER(vp), C.POINTER(vp), vp, vp, vp, vp, vp, vp]
             cf = C.c_float
             L.duck_clip_adam.argtypes = [ci, vp, vp, vp, vp, vp, vp, cf, cf, cf, cf, cf, vp]
             L.duck_clip_adam_scratch_size.argtypes = [ci]

@@ -62,6 +62,9 @@ class PPOConfig:
     policy_obs_key: str = "state"
     value_obs_key: str = "privileged_state"
     seed: int = 0
+    # brax's name: episode/* means over the training episodes that finish during an update (EpisodeWrapper's
+    # episode_metrics), accumulated on the device inside the rollout graph
+    log_training_metrics: bool = False
 
 
 # ---------------------------------------------------------------------------------------
@@ -834,6 +837,21 @@ class _Rollout:
         self.ctr = torch.zeros(1, dtype=torch.int32, device=dev)
         self.seed = (int(seed) * 0x9E3779B97F4A7C15 + 0x5EED) & 0xFFFFFFFFFFFFFFFF
         self.use_graph, self.calls, self.graph = use_graph, 0, None
+        # log_training_metrics: duck_episode_accumulate(TRAIN) after every env-step; run / fin / flag persist
+        # across updates (an episode usually spans several), train() reads and zeroes fin / flag per update
+        self.episode = None
+        if cfg.log_training_metrics and hasattr(env, "METRICS") and hasattr(env, "_layout"):
+            F_ = len(env.METRICS) + 2
+            self.episode = {"names": list(env.METRICS), "run": torch.zeros(n, F_, device=dev),
+                            "fin": torch.zeros(n, F_, device=dev), "flag": torch.zeros(n, device=dev)}
+
+    def episode_report(self) -> Dict[str, float]:
+        """episode/* of the episodes that finished since the last call (all ranks); zeroes fin / flag."""
+        ep = self.episode
+        out = episode_report(ep["fin"], ep["flag"], ep["names"])
+        ep["fin"].zero_()
+        ep["flag"].zero_()
+        return out
 
     def _policy(self, obs: torch.Tensor, st) -> torch.Tensor:
         from .native import check
@@ -889,6 +907,12 @@ class _Rollout:
                                                   data["raw_action"][t, cols].data_ptr(),
                                                   data["log_prob"][t, cols].data_ptr(), self.action.data_ptr(), st))
                 self.env.step(state, self.action, inplace=True)  # obs already copied out
+                if self.episode is not None:
+                    ep = self.episode
+                    check(self.lib.duck_episode_accumulate(
+                        n, len(ep["names"]), state.reward.data_ptr(), state.done.data_ptr(),
+                        state.fstate.data_ptr() + 4 * self.env._layout.off["metrics"] * n, n, EPISODE_TRAIN,
+                        ep["run"].data_ptr(), ep["fin"].data_ptr(), ep["flag"].data_ptr(), st))
                 # the transition's outcome, and the observations the next env-step starts from (the
                 # state's obs after this step: they are row t + 1 of obs / priv, and next_priv's last row
                 # -- the only one the learner reads, the bootstrap observation)
@@ -1011,8 +1035,9 @@ def train(env, cfg: PPOConfig, progress_fn: Optional[Callable[[int, dict], None]
     result = TrainResult(net=net)
     # brax: num_evals evaluations spread evenly over training, the first before any update
     eval_every = max(1, n_updates // max(1, cfg.num_evals - 1)) if cfg.num_evals > 1 else None
-    if eval_env is not None and cfg.num_evals > 0 and rank == 0:
-        m0 = evaluate(net, eval_env, cfg, rng=cfg.seed + 10_007)
+    evaluator = Evaluator(net, eval_env, cfg) if eval_env is not None and rank == 0 else None
+    if evaluator is not None and cfg.num_evals > 0:
+        m0 = evaluator.run(rng=cfg.seed + 10_007)
         if progress_fn is not None:
             progress_fn(0, m0)
     t0 = time.time()
@@ -1052,9 +1077,11 @@ def train(env, cfg: PPOConfig, progress_fn: Optional[Callable[[int, dict], None]
         metrics = {"train/reward_per_step": float(rew),
                    **{f"train/{k}": float(v) for k, v in last.items()},
                    "env_steps": result.env_steps, "sps": result.env_steps / (time.time() - t0)}
+        if roller is not None and roller.episode is not None:
+            metrics.update(roller.episode_report())
         if eval_env is not None and rank == 0 and eval_every is not None and (
                 (upd + 1) % eval_every == 0 or upd + 1 == n_updates):
-            metrics.update(evaluate(net, eval_env, cfg, rng=cfg.seed + 10_007 + upd))
+            metrics.update(evaluator.run(rng=cfg.seed + 10_007 + upd))
             if policy_params_fn is not None:
                 policy_params_fn(result.env_steps, net)
         result.metrics.append(metrics)
@@ -1064,29 +1091,208 @@ def train(env, cfg: PPOConfig, progress_fn: Optional[Callable[[int, dict], None]
     return result
 
 
-@torch.no_grad()
-def evaluate(net: ActorCritic, eval_env, cfg: PPOConfig, rng: int) -> Dict[str, float]:
-    """brax Evaluator: one episode per eval env with the deterministic policy (tanh(loc)).
+POLICY_ACT_MAX_LAYERS, POLICY_ACT_MAX_WIDTH = 4, 512   # duck_policy_act (include/duck_ppo.h)
+EPISODE_EVAL, EPISODE_TRAIN = 0, 1                      # duck_episode_accumulate's modes
 
-    ``eval_env`` is wrapped like the training env (auto-reset); as brax's EvalWrapper does,
-    each env's return stops accumulating at its first ``done``.
-    """
-    state = eval_env.reset(rng=rng)
-    n = eval_env.num_envs
-    ret = torch.zeros(n, device=eval_env.device)
-    length = torch.zeros(n, device=eval_env.device)
-    active = torch.ones(n, device=eval_env.device)
-    for _ in range(cfg.episode_length // cfg.action_repeat):
-        act = NormalTanh(net.policy_logits(state.obs[cfg.policy_obs_key])).mode()
-        eval_env.step(state, act, inplace=True)
-        ret += state.reward * active
-        length += active
-        active = active * (1.0 - state.done)
-    if eval_env.device.type == "cuda":
-        torch.cuda.synchronize(eval_env.device)
-    check_device_error(eval_env, "evaluation")   # the last launch is not followed by another duck_step
-    return {"eval/episode_reward": float(ret.mean()), "eval/episode_reward_std": float(ret.std(unbiased=False)),
-            "eval/avg_episode_length": float(length.mean())}
+
+def _mean_std(s: float, ss: float, n: int):
+    """Mean and population std over n values from their fp64 sum and sum of squares."""
+    mean = s / n
+    return mean, math.sqrt(max(0.0, ss / n - mean * mean))
+
+
+def _column_sums(x: torch.Tensor) -> torch.Tensor:
+    """[column sums | column sums of squares] of x [N, F] in fp64 on the host: duck_column_stats for fp32 GPU
+    tensors (fixed summation order), torch's fp64 reductions otherwise."""
+    x = x.contiguous()
+    if not (x.is_cuda and x.dtype == torch.float32):
+        x = x.double()
+        return torch.cat([x.sum(0), (x * x).sum(0)]).cpu()
+    from .native import check, lib
+    L = lib()
+    n, k = x.shape
+    scratch = torch.empty(max(1, L.duck_column_stats_scratch(n, k)), dtype=torch.float64, device=x.device)
+    out = torch.empty(2 * k, dtype=torch.float64, device=x.device)
+    check(L.duck_column_stats(n, k, x.data_ptr(), out.data_ptr(), scratch.data_ptr(),
+                              torch.cuda.current_stream(x.device).cuda_stream))
+    return out.cpu()
+
+
+def _policy_act_fits(net: ActorCritic) -> bool:
+    lin = [m for m in net.policy if isinstance(m, nn.Linear)]
+    widths = [lin[0].in_features] + [m.out_features for m in lin]
+    return len(lin) <= POLICY_ACT_MAX_LAYERS and max(widths) <= POLICY_ACT_MAX_WIDTH and widths[-1] % 2 == 0
+
+
+def policy_act_args(net: ActorCritic):
+    """duck_policy_act's host arguments for the policy of ``net`` as it is now: (nlayers, sizes, W, b, mean,
+    istd) -- live pointers: parameters and normaliser are updated in place, so a captured launch keeps reading
+    the current policy -- and a key that changes when any of them moved."""
+    lin = [m for m in net.policy if isinstance(m, nn.Linear)]
+    sizes = (C.c_int * (len(lin) + 1))(lin[0].in_features, *[m.out_features for m in lin])
+    W = (C.c_void_p * len(lin))(*[m.weight.data_ptr() for m in lin])
+    b = (C.c_void_p * len(lin))(*[m.bias.data_ptr() for m in lin])
+    mean, istd = (net.obs_norm.mean32.data_ptr(), net.obs_norm.istd32.data_ptr()) if net.normalize else (None, None)
+    for m in lin:
+        if m.weight.dtype != torch.float32 or not m.weight.is_contiguous() or not m.bias.is_contiguous():
+            raise ValueError("duck_policy_act takes contiguous float32 parameters")
+    return (len(lin), sizes, W, b, mean, istd), (tuple(W), tuple(b), mean, istd)
+
+
+def episode_report(fin: torch.Tensor, flag: torch.Tensor, names) -> Dict[str, float]:
+    """The ``episode/*`` training metrics (brax EpisodeWrapper's episode_metrics as brax PPO logs them) from
+    duck_episode_accumulate(TRAIN)'s buffers: fin [n, F] holds, per env, the column sums (reward, the metrics
+    in ``names``' order, steps) of the episodes that finished since it was zeroed, flag [n] their number.
+    Means over those episodes, all ranks' together; all 0 when none finished."""
+    F_ = fin.shape[1]
+    tot = torch.cat([_column_sums(fin)[:F_], _column_sums(flag.reshape(-1, 1))[:1]])
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        tot = tot.to(fin.device)
+        dist.all_reduce(tot)   # the sums and the counts, before dividing
+        tot = tot.cpu()
+    count = float(tot[F_])
+    mean = [float(v) / count if count > 0 else 0.0 for v in tot[:F_]]
+    out = {"episode/sum_reward": mean[0], "episode/length": mean[F_ - 1]}
+    out.update({f"episode/{name}": mean[1 + k] for k, name in enumerate(names) if name})
+    out["episode/count"] = count
+    return out
+
+
+class Evaluator:
+    """brax Evaluator: one episode per eval env with the deterministic policy (tanh(loc)); ``eval_env`` is
+    wrapped like the training env (auto-reset) and, as brax's EvalWrapper does, every accumulator of an env
+    stops at its first ``done``. Reports the episode return, length and every ``state.metrics`` term (mean and
+    population std over the envs), the evaluation's wall time and env-steps per second.
+
+    On the GPU with a Joystick env and a policy within duck_policy_act's limits an env-step is three launches
+    -- duck_policy_act (the whole policy; logits bit-identical to the rollout's duck_mlp_gemm chain), duck_step,
+    duck_episode_accumulate -- captured once on one stream as a graph of ``CHUNK`` env-steps and replayed (the
+    remainder runs eagerly, as does the whole first evaluation and every one under DUCK_PPO_GRAPH=0). The graph
+    reads the live parameters and normaliser. Elsewhere (CPU, toy envs, wider policies, DUCK_PPO_FUSED_MLP=0)
+    the torch loop runs."""
+
+    CHUNK = 200   # env-steps per captured graph (600 launches, the size of the rollout's graph)
+
+    def __init__(self, net: ActorCritic, eval_env, cfg: PPOConfig, use_graph: Optional[bool] = None):
+        self.net, self.env, self.cfg = net, eval_env, cfg
+        self.n, self.device = eval_env.num_envs, torch.device(eval_env.device)
+        self.steps = cfg.episode_length // cfg.action_repeat
+        self.native = fused_grad_available(self.device) and hasattr(eval_env, "METRICS") and \
+            hasattr(eval_env, "_layout") and _policy_act_fits(net) and \
+            net.policy[0].in_features == eval_env.observation_size[cfg.policy_obs_key][0]
+        if use_graph is None:
+            use_graph = os.environ.get("DUCK_PPO_GRAPH", "1") != "0"
+        self.use_graph = bool(use_graph) and self.native
+        self.calls, self.graph, self.graph_key, self.state = 0, None, None, None
+        self.acc = None   # [n, F] per-env accumulators of the last evaluation: reward, metrics, steps
+        if self.native:
+            from .native import lib
+            self.lib = lib()
+            self.names = list(eval_env.METRICS)
+            F_ = len(self.names) + 2
+            self.acc = torch.zeros(self.n, F_, device=self.device)
+            self.active = torch.ones(self.n, device=self.device)
+            self.action = torch.empty(self.n, net.policy[-1].out_features // 2, device=self.device)
+            self.stats = torch.empty(2 * F_, dtype=torch.float64, device=self.device)
+            self.scratch = torch.empty(max(1, self.lib.duck_column_stats_scratch(self.n, F_)), dtype=torch.float64,
+                                       device=self.device)
+
+    # ---- native path ----
+    def _run_steps(self, k: int, args) -> None:
+        from .native import check
+        env, st, n = self.env, self.state, self.n
+        L = env._layout
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        obs = st.obs[self.cfg.policy_obs_key]
+        metrics = st.fstate.data_ptr() + 4 * L.off["metrics"] * n   # the SoA rows, stride n
+        for _ in range(k):
+            check(self.lib.duck_policy_act(n, *args, obs.data_ptr(), None, self.action.data_ptr(), stream))
+            env.step(st, self.action, inplace=True)
+            check(self.lib.duck_episode_accumulate(n, len(self.names), st.reward.data_ptr(), st.done.data_ptr(),
+                                                   metrics, n, EPISODE_EVAL, self.acc.data_ptr(), None,
+                                                   self.active.data_ptr(), stream))
+
+    def _native(self, rng: int) -> Dict[str, float]:
+        from .native import check
+        self.state = self.env.reset(rng=rng, state=self.state)   # outside the graph: rng changes
+        self.acc.zero_()
+        self.active.fill_(1.0)
+        args, key = policy_act_args(self.net)
+        self.calls += 1
+        if not self.use_graph or self.calls == 1:
+            self._run_steps(self.steps, args)
+        else:
+            chunk = max(1, min(self.steps, self.CHUNK))
+            if self.graph is None or self.graph_key != (key, chunk):   # (a parameter tensor that moved: recapture)
+                self.graph, self.graph_key = torch.cuda.CUDAGraph(), (key, chunk)
+                with torch.cuda.graph(self.graph):   # one capture stream: a linear graph
+                    self._run_steps(chunk, args)
+            for _ in range(self.steps // chunk):
+                self.graph.replay()
+            self._run_steps(self.steps % chunk, args)
+        torch.cuda.synchronize(self.device)
+        check_device_error(self.env, "evaluation")   # a replayed graph never re-enters duck_step's entry check
+        F_ = self.acc.shape[1]
+        check(self.lib.duck_column_stats(self.n, F_, self.acc.data_ptr(), self.stats.data_ptr(),
+                                         self.scratch.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream))
+        return self._report(self.stats.cpu().tolist(), self.names)
+
+    def _report(self, stats, names) -> Dict[str, float]:
+        F_, n = len(names) + 2, self.n
+        ms = [_mean_std(stats[c], stats[F_ + c], n) for c in range(F_)]
+        out = {"eval/episode_reward": ms[0][0], "eval/episode_reward_std": ms[0][1],
+               "eval/avg_episode_length": ms[F_ - 1][0], "eval/std_episode_length": ms[F_ - 1][1]}
+        for k, name in enumerate(names):
+            if name:
+                out[f"eval/episode_{name}"], out[f"eval/episode_{name}_std"] = ms[1 + k]
+        return out
+
+    # ---- torch path ----
+    def _torch(self, rng: int) -> Dict[str, float]:
+        net, eval_env, cfg = self.net, self.env, self.cfg
+        state = eval_env.reset(rng=rng)
+        n = eval_env.num_envs
+        ret = torch.zeros(n, device=eval_env.device)
+        length = torch.zeros(n, device=eval_env.device)
+        active = torch.ones(n, device=eval_env.device)
+        has = isinstance(getattr(state, "metrics", None), dict)
+        names = [k for k in state.metrics if k] if has else []
+        macc = {k: torch.zeros(n, device=eval_env.device) for k in names}
+        for _ in range(cfg.episode_length // cfg.action_repeat):
+            act = NormalTanh(net.policy_logits(state.obs[cfg.policy_obs_key])).mode()
+            eval_env.step(state, act, inplace=True)
+            ret += state.reward * active
+            length += active
+            for k in names:
+                macc[k] += state.metrics[k] * active
+            active = active * (1.0 - state.done)
+        if eval_env.device.type == "cuda":
+            torch.cuda.synchronize(eval_env.device)
+        check_device_error(eval_env, "evaluation")   # the last launch is not followed by another duck_step
+        self.acc = torch.stack([ret] + [macc[k] for k in names] + [length], 1)
+        a = self.acc.double()
+        out = self._report(torch.cat([a.sum(0), (a * a).sum(0)]).tolist(), names)
+        out.update({"eval/episode_reward": float(ret.mean()), "eval/episode_reward_std": float(ret.std(unbiased=False)),
+                    "eval/avg_episode_length": float(length.mean())})
+        return out
+
+    @torch.no_grad()
+    def run(self, rng: int) -> Dict[str, float]:
+        t0 = time.time()
+        out = self._native(rng) if self.native else self._torch(rng)
+        dt = time.time() - t0
+        out["eval/epoch_eval_time"] = dt
+        out["eval/sps"] = self.steps * self.n / max(dt, 1e-9)
+        return out
+
+
+def evaluate(net: ActorCritic, eval_env, cfg: PPOConfig, rng: int) -> Dict[str, float]:
+    """One evaluation by the ``Evaluator`` of (net, eval_env, cfg): kept on the env between calls, so its
+    buffers and captured graph serve every evaluation of a training run."""
+    ev = getattr(eval_env, "_evaluator", None)
+    if ev is None or ev.net is not net or ev.cfg != cfg:
+        ev = eval_env._evaluator = Evaluator(net, eval_env, cfg)
+    return ev.run(rng)
 
 
 def save_checkpoint(net: ActorCritic, cfg: PPOConfig, path: str) -> None:

@@ -64,7 +64,8 @@ class BaseRunner:
         export_onnx(net, self.action_size, self.obs_size, output_path=f"{self.output_dir}/{d}_{current_step}.onnx")
 
     def make_ppo_params(self) -> PPOConfig:
-        return replace(PPOConfig(), num_timesteps=self.num_timesteps)
+        return replace(PPOConfig(), num_timesteps=self.num_timesteps,
+                       log_training_metrics=bool(getattr(self.args, "log_training_metrics", False)))
 
     def train(self, max_updates=None):
         self.ppo_params = self.make_ppo_params()
@@ -116,6 +117,8 @@ def main(argv=None) -> None:
     parser.add_argument("--restore_checkpoint_path", type=str, default=None,
                         help="Resume training from this checkpoint")
     parser.add_argument("--num_eval_envs", type=int, default=128, help="brax ppo.train default")
+    parser.add_argument("--log_training_metrics", action="store_true",
+                        help="log episode/* means over the training episodes that finish during each update")
     parser.add_argument("--max_updates", type=int, default=None, help="stop after this many PPO updates")
     args = parser.parse_args(argv)
     if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) > 1 and not dist.is_initialized():
