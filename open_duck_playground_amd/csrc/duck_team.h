@@ -595,7 +595,38 @@ struct TPhys {
   }
 
   // ---------------- mj_comPos: subtree com (team reduction), cinert, cdof ----------------
-  static DK void com_pos(LP L, int lane) {
+  // com_pos's words that kinematics does not write, a prologue that may run while kinematics still works:
+  //   ip (bodies > 1), Bi, I, jb, jda, jtype, ja  words of the model table (never written after the
+  //                                               launch's table copy)
+  //   ip (body 1), m                              per-env model values (DIPOS, DMASS: constant through
+  //                                               the launch)
+  static constexpr int NJS = (NJ + TEAM - 1) / TEAM;
+  struct ComPre {
+    float ip[3], Bi[9], I[3], m;
+    int jb[NJS], jda[NJS], jtype[NJS];
+    float ja[NJS][3];
+  };
+  static DK ComPre com_pre(LP L, int lane) {
+    ComPre P;
+    const int b = 1 + lane, bc = b < NB ? b : 1;  // (unmasked loads: lanes past the bodies read body 1)
+    const int ob = Md::B_BINERT + 17 * bc;
+    for (int k = 0; k < 3; k++) P.ip[k] = (b == 1) ? L[Ly::DIPOS + k] : tf(ob + k);
+    for (int k = 0; k < 9; k++) P.Bi[k] = tf(ob + 3 + k);
+    for (int k = 0; k < 3; k++) P.I[k] = tf(ob + 12 + k);
+    P.m = L[Ly::DMASS + bc];
+#pragma unroll
+    for (int s = 0; s < NJS; s++) {
+      const int j = lane + TEAM * s, jc = j < NJ ? j : 0, oj = Md::B_JREC + 9 * jc;
+      // affine joint maps (codegen B_JAFF): hinge j >= B_JN0 sits on body j + B_JBD with dof j + B_JDD
+      const bool jh = Md::B_JAFF && jc >= Md::B_JN0;
+      P.jb[s] = jh ? jc + Md::B_JBD : ti(oj);
+      P.jda[s] = jh ? jc + Md::B_JDD : ti(oj + 1);
+      P.jtype[s] = jh ? 3 : ti(oj + 3);
+      for (int k = 0; k < 3; k++) P.ja[s][k] = tf(oj + 4 + k);
+    }
+    return P;
+  }
+  static DK void com_pos(LP L, int lane, const ComPre& P) {
 #pragma clang fp reassociate(on)
     // every moving body fits the team (a body per lane): its inertial frame (xipos, the rotated
     // inertia) is formed once, held across the subtree-com reduction, and only the offset from the
@@ -605,19 +636,18 @@ struct TPhys {
     const int b = 1 + lane;
     const bool mv = b < NB && moving(b);
     if (mv) {
-      const int ob = Md::B_BINERT + 17 * b;
       float R[9], t[3], ip[3], Ri[9], Bi[9];
       for (int k = 0; k < 9; k++) R[k] = L[Ly::XMAT + Ly::XMS * b + k];
-      for (int k = 0; k < 3; k++) ip[k] = (b == 1) ? L[Ly::DIPOS + k] : tf(ob + k);
-      for (int k = 0; k < 9; k++) Bi[k] = tf(ob + 3 + k);
+      for (int k = 0; k < 3; k++) ip[k] = P.ip[k];
+      for (int k = 0; k < 9; k++) Bi[k] = P.Bi[k];
       mulmv3(t, R, ip);
       mulmm3(Ri, R, Bi);
-      const float I[3] = {tf(ob + 12), tf(ob + 13), tf(ob + 14)};
+      const float I[3] = {P.I[0], P.I[1], P.I[2]};
       for (int a = 0; a < 3; a++)
         for (int c = 0; c < 3; c++)
           rot[3 * a + c] = Ri[3 * a] * I[0] * Ri[3 * c] + Ri[3 * a + 1] * I[1] * Ri[3 * c + 1] + Ri[3 * a + 2] * I[2] * Ri[3 * c + 2];
       for (int k = 0; k < 3; k++) xi[k] = L[Ly::XPOS + Ly::XPS * b + k] + t[k];
-      m = L[Ly::DMASS + b];
+      m = P.m;
     }
     const float ms = tsum(m);
     const float inv = frcp(ms);
@@ -637,32 +667,35 @@ struct TPhys {
       L[o + 6] = m * d[0]; L[o + 7] = m * d[1]; L[o + 8] = m * d[2];
       L[o + 9] = m;
     }
-    team_for<NJ>(lane, [&](int j) {
-      const int oj = Md::B_JREC + 9 * j;
-      // affine joint maps (codegen B_JAFF): hinge j >= B_JN0 sits on body j + B_JBD with dof j + B_JDD
-      const bool jh = Md::B_JAFF && j >= Md::B_JN0;
-      const int b = jh ? j + Md::B_JBD : ti(oj), da = jh ? j + Md::B_JDD : ti(oj + 1);
+#pragma unroll
+    for (int s = 0; s < NJS; s++) {
+      const int j = lane + TEAM * s;
+      if (NJ % TEAM != 0 && s == NJS - 1 && j >= NJ) continue;
+      const int b = P.jb[s], da = P.jda[s];
+      // the joint's body frame before either branch's stores: the free joint's axes are R's columns, and
+      // read one column at a time between the cdof stores each column cost an LDS round trip
+      float R[9];
+      for (int k = 0; k < 9; k++) R[k] = L[Ly::XMAT + Ly::XMS * b + k];
       const float off[3] = {com[0] - L[Ly::XPOS + Ly::XPS * b], com[1] - L[Ly::XPOS + Ly::XPS * b + 1], com[2] - L[Ly::XPOS + Ly::XPS * b + 2]};
-      if (!jh && ti(oj + 3) == 0) {
+      if (P.jtype[s] == 0) {
         for (int k = 0; k < 3; k++)
           for (int q = 0; q < 6; q++) L[Ly::CDOF + 6 * (da + k) + q] = (q == 3 + k) ? 1.0f : 0.0f;
         for (int k = 0; k < 3; k++) {
-          const float ax[3] = {L[Ly::XMAT + Ly::XMS * b + k], L[Ly::XMAT + Ly::XMS * b + 3 + k], L[Ly::XMAT + Ly::XMS * b + 6 + k]};
+          const float ax[3] = {R[k], R[3 + k], R[6 + k]};
           float t[3];
           cross3(t, ax, off);
           const int o = Ly::CDOF + 6 * (da + 3 + k);
           L[o] = ax[0]; L[o + 1] = ax[1]; L[o + 2] = ax[2]; L[o + 3] = t[0]; L[o + 4] = t[1]; L[o + 5] = t[2];
         }
       } else {
-        float R[9], ax[3], t[3];
-        const float ja[3] = {tf(oj + 4), tf(oj + 5), tf(oj + 6)};
-        for (int k = 0; k < 9; k++) R[k] = L[Ly::XMAT + Ly::XMS * b + k];
+        float ax[3], t[3];
+        const float ja[3] = {P.ja[s][0], P.ja[s][1], P.ja[s][2]};
         mulmv3(ax, R, ja);
         cross3(t, ax, off);
         const int o = Ly::CDOF + 6 * da;
         L[o] = ax[0]; L[o + 1] = ax[1]; L[o + 2] = ax[2]; L[o + 3] = t[0]; L[o + 4] = t[1]; L[o + 5] = t[2];
       }
-    });
+    }
     TSYNC();
   }
 
@@ -673,88 +706,130 @@ struct TPhys {
   // suffix sums per lane, a team sum at the trunk, the root path on every lane.
   static constexpr int RCA = TL::RCA, RFB = TL::RFB;  // body accelerations / body forces (scratch)
 
-  // cvel/cacc of the free-joint root body (every lane); its cdof_dot rows go to CDD1 (sensors)
-  static DK void root_motion(LP L, int lane, int b, float* cv, float* ca) {
+  // the cdof rows and velocities of a root-path body's dofs (a free joint's translational rows are unit
+  // vectors: only rows 3-5 are read)
+  struct RootIn { float cd[3][6], qv[6]; };
+  static constexpr bool root_dofs_fit() {
+    for (int r = 0; r < Md::T_NROOT; r++) {
+      const int nd = Md::body_dofnum[Md::T_ROOT[r]];
+      if (nd != 6 && nd > 3) return false;
+    }
+    return true;
+  }
+  static_assert(root_dofs_fit(), "RootIn holds three cdof rows per root-path body");
+  static DK void root_load(LP L, int b, RootIn& I) {
     const int da = Md::body_dofadr[b], nd = Md::body_dofnum[b];
     if (nd == 6) {
+      for (int i = 0; i < 6; i++) I.qv[i] = L[Ly::QVEL + da + i];
+      for (int i = 3; i < 6; i++)
+        for (int k = 0; k < 6; k++) I.cd[i - 3][k] = L[Ly::CDOF + 6 * (da + i) + k];
+    } else {
+      for (int jj = 0; jj < nd; jj++) {
+        for (int k = 0; k < 6; k++) I.cd[jj][k] = L[Ly::CDOF + 6 * (da + jj) + k];
+        I.qv[jj] = L[Ly::QVEL + da + jj];
+      }
+    }
+  }
+  // cvel/cacc of the free-joint root body (every lane); its cdof_dot rows go to CDD1 (sensors)
+  static DK void root_motion(LP L, int lane, int b, const RootIn& I, float* cv, float* ca) {
+    const int nd = Md::body_dofnum[b];
+    if (nd == 6) {
       // free joint: the translational cdof rows are the unit vectors e_3..e_5 (com_pos)
-      for (int i = 0; i < 3; i++) cv[3 + i] += L[Ly::QVEL + da + i];
+      for (int i = 0; i < 3; i++) cv[3 + i] += I.qv[i];
       float cvt[6];
       for (int k = 0; k < 6; k++) cvt[k] = cv[k];
       for (int i = 3; i < 6; i++) {
         float cd[6], cdd[6];
-        for (int k = 0; k < 6; k++) cd[k] = L[Ly::CDOF + 6 * (da + i) + k];
+        for (int k = 0; k < 6; k++) cd[k] = I.cd[i - 3][k];
         cross_motion(cdd, cvt, cd);
         if (lane == i - 3)
           for (int k = 0; k < 6; k++) L[Ly::CDD1 + 6 * (i - 3) + k] = cdd[k];
-        const float v = L[Ly::QVEL + da + i];
+        const float v = I.qv[i];
         for (int k = 0; k < 6; k++) { ca[k] += cdd[k] * v; cv[k] += cd[k] * v; }
       }
     } else {
       for (int jj = 0; jj < nd; jj++) {
         float cd[6], cdd[6];
-        for (int k = 0; k < 6; k++) cd[k] = L[Ly::CDOF + 6 * (da + jj) + k];
+        for (int k = 0; k < 6; k++) cd[k] = I.cd[jj][k];
         cross_motion(cdd, cv, cd);
-        const float v = L[Ly::QVEL + da + jj];
+        const float v = I.qv[jj];
         for (int k = 0; k < 6; k++) { ca[k] += cdd[k] * v; cv[k] += cd[k] * v; }
       }
     }
   }
 
+  // rne_vel's words that com_pos does not write, a prologue that may run while com_pos still works:
+  //   bb, dof  the lane's limb bodies and their dofs: words of the model table (never written after the
+  //            launch's table copy)
+  //   qv       QVEL of those dofs: written by euler() and the env code only
+  static constexpr int RBL = Md::T_BRLEN, RMD = Md::T_BRMD;  // bodies per limb, dofs per limb body (2: backlash)
+  struct RnePre {
+    int bb[RBL], dof[RBL][RMD];
+    float qv[RBL][RMD];
+  };
+  static DK RnePre rne_pre(LP L, int lane) {
+    RnePre P;
+#pragma unroll
+    for (int d = 0; d < RBL; d++) P.bb[d] = limb_body(lane, d);
+#pragma unroll
+    for (int d = 0; d < RBL; d++)
+#pragma unroll
+      for (int jj = 0; jj < RMD; jj++) P.dof[d][jj] = limb_dof(lane, 2 * d + jj);
+#pragma unroll
+    for (int d = 0; d < RBL; d++)
+#pragma unroll
+      for (int jj = 0; jj < RMD; jj++) P.qv[d][jj] = L[Ly::QVEL + (P.dof[d][jj] >= 0 ? P.dof[d][jj] : 0)];
+    return P;
+  }
   // PART 0: the whole pass (throughput mode). Latency mode: wave 0 runs rne_vel, then rne_rest<1>
   // (the composite-inertia lanes of phase C write a dump region), wave 1 runs subtree_sums<2> (the
   // composite inertias only: they need com_pos, not the velocities), so crb starts before rne ends
-  static DK void rne(LP L, int lane) {
-    rne_vel(L, lane);
+  static DK void rne(LP L, int lane, const RnePre& P) {
+    rne_vel(L, lane, P);
     rne_rest<0>(L, lane);
   }
   // (A) velocities and accelerations
-  static DK void rne_vel(LP L, int lane) {
+  static DK void rne_vel(LP L, int lane, const RnePre& P) {
 #pragma clang fp reassociate(on)
     STAGE_T0();
-    constexpr int NR = Md::T_NROOT, BL = Md::T_BRLEN, MD = Md::T_BRMD;  // dofs per limb body (2: backlash)
+    constexpr int NR = Md::T_NROOT, BL = RBL, MD = RMD;
     static_assert(Md::T_NBR <= TEAM, "a limb per lane");
+    // every cdof row and velocity of the pass first, in one batch: the stores of the root path (lane 0,
+    // the cdof_dot rows) and of the limb chain stand between the bodies, and a load cannot pass a store,
+    // so read where they were used each root-path body and the limbs cost an LDS round trip of their own
+    RootIn ri[NR];
+#pragma unroll
+    for (int r = 0; r < NR; r++) root_load(L, Md::T_ROOT[r], ri[r]);
+    float cd[BL][MD][6], qv[BL][MD];
+#pragma unroll
+    for (int d = 0; d < BL; d++)
+#pragma unroll
+      for (int jj = 0; jj < MD; jj++) {
+        const int i = P.dof[d][jj] >= 0 ? P.dof[d][jj] : 0;
+        for (int k = 0; k < 6; k++) cd[d][jj][k] = L[Ly::CDOF + 6 * i + k];
+        qv[d][jj] = P.dof[d][jj] >= 0 ? P.qv[d][jj] : 0.0f;  // unconditional load, then select (no masked load)
+      }
     float cv[6], ca[6];
     for (int k = 0; k < 6; k++) { cv[k] = 0.0f; ca[k] = (k >= 3) ? -Md::gravity[k - 3] : 0.0f; }
 #pragma unroll
     for (int r = 0; r < NR; r++) {
       const int b = Md::T_ROOT[r];
-      root_motion(L, lane, b, cv, ca);
+      root_motion(L, lane, b, ri[r], cv, ca);
       if (lane == 0)
         for (int k = 0; k < 6; k++) { L[Ly::CVEL + 6 * b + k] = cv[k]; L[RCA + 6 * b + k] = ca[k]; }
     }
     const bool limb = lane < Md::T_NBR;
-    int bb[BL];
 #pragma unroll
-    for (int d = 0; d < BL; d++) bb[d] = limb_body(lane, d);
-    {
-      float cd[BL][MD][6], qv[BL][MD];
-      int dof[BL][MD];
+    for (int d = 0; d < BL; d++) {
 #pragma unroll
-      for (int d = 0; d < BL; d++)
-#pragma unroll
-        for (int jj = 0; jj < MD; jj++) dof[d][jj] = limb_dof(lane, 2 * d + jj);
-#pragma unroll
-      for (int d = 0; d < BL; d++)
-#pragma unroll
-        for (int jj = 0; jj < MD; jj++) {
-          const int i = dof[d][jj] >= 0 ? dof[d][jj] : 0;
-          for (int k = 0; k < 6; k++) cd[d][jj][k] = L[Ly::CDOF + 6 * i + k];
-          const float q = L[Ly::QVEL + i];  // unconditional load, then select (no masked load)
-          qv[d][jj] = dof[d][jj] >= 0 ? q : 0.0f;
-        }
-#pragma unroll
-      for (int d = 0; d < BL; d++) {
-#pragma unroll
-        for (int jj = 0; jj < MD; jj++) {
-          float cdd[6];
-          cross_motion(cdd, cv, cd[d][jj]);
-          const float v = qv[d][jj];
-          for (int k = 0; k < 6; k++) { ca[k] += cdd[k] * v; cv[k] += cd[d][jj][k] * v; }
-        }
-        if (limb && bb[d] >= 0)
-          for (int k = 0; k < 6; k++) { L[Ly::CVEL + 6 * bb[d] + k] = cv[k]; L[RCA + 6 * bb[d] + k] = ca[k]; }
+      for (int jj = 0; jj < MD; jj++) {
+        float cdd[6];
+        cross_motion(cdd, cv, cd[d][jj]);
+        const float v = qv[d][jj];
+        for (int k = 0; k < 6; k++) { ca[k] += cdd[k] * v; cv[k] += cd[d][jj][k] * v; }
       }
+      if (limb && P.bb[d] >= 0)
+        for (int k = 0; k < 6; k++) { L[Ly::CVEL + 6 * P.bb[d] + k] = cv[k]; L[RCA + 6 * P.bb[d] + k] = ca[k]; }
     }
     TSYNC();
     STAGE_MARK(ST_RNE_A);
@@ -953,21 +1028,56 @@ struct TPhys {
   }
 
   // ---------------- actuation + passive; H = M ----------------
-  static DK void smooth(LP L, int lane) {
+  // smooth's inputs, a prologue that may run before the stage ahead of smooth (crb, which writes M and the
+  // zero word only) has finished:
+  //   damp, dof, clim .. fhi  words of the model table (never written after the launch's table copy)
+  //   kp                      per-env model value (DKP: constant through the launch)
+  //   c                       CTRL: written by the env code before the substeps only
+  //   qv, qp, qd              QPOS / QVEL: written by euler() and the env code only
+  //   fsm                     FSM of the lane's dofs: written by rne_rest, which ends with a sync of its own
+  //                           (by the same lane, team_for<NV>)
+  static constexpr int NVS = (NV + TEAM - 1) / TEAM;
+  struct SmoothPre {
+    float damp[NVS], qv[NVS], fsm[NVS];
+    int dof, clim, flim;
+    float c, clo, chi, g, kp, qp, qd, kv, flo, fhi;
+  };
+  static DK SmoothPre smooth_pre(LP L, int lane) {
+    SmoothPre P;
+#pragma unroll
+    for (int s = 0; s < NVS; s++) {
+      const int i = lane + TEAM * s, ic = i < NV ? i : 0;  // (unmasked loads: lanes past NV read dof 0)
+      P.damp[s] = tf(Md::B_DAMP + ic); P.qv[s] = L[Ly::QVEL + ic]; P.fsm[s] = L[Ly::FSM + ic];
+    }
+    const int a = lane < NU ? lane : 0, o = Md::B_ACT + 12 * a;  // (lanes past NU read actuator 0)
+    P.dof = act_dof(a);
+    P.clim = ti(o); P.clo = tf(o + 1); P.chi = tf(o + 2);
+    P.g = tf(o + 3); P.kv = tf(o + 6);
+    P.flim = ti(o + 7); P.flo = tf(o + 8); P.fhi = tf(o + 9);
+    P.c = L[Ly::CTRL + a];
+    P.kp = L[Ly::DKP + a];
+    P.qp = L[Ly::QPOS + act_qadr(a)];
+    P.qd = L[Ly::QVEL + P.dof];
+    return P;
+  }
+  static DK void smooth(LP L, int lane, const SmoothPre& P) {
     ASM_MARK("SMOOTH_BEGIN");
-    team_for<NV>(lane, [&](int i) { L[Ly::FSM + i] += -tf(Md::B_DAMP + i) * L[Ly::QVEL + i]; });
+#pragma unroll
+    for (int s = 0; s < NVS; s++) {
+      const int i = lane + TEAM * s;
+      if (TEAM * (s + 1) <= NV || i < NV) L[Ly::FSM + i] = P.fsm[s] + -P.damp[s] * P.qv[s];
+    }
     TSYNC();
     if (lane < NU) {
-      const int a = lane, o = Md::B_ACT + 12 * a;
-      const int dof = act_dof(a);
-      float c = L[Ly::CTRL + a];
-      if (ti(o)) c = fminf(fmaxf(c, tf(o + 1)), tf(o + 2));
-      const float g = tf(o + 3), kp = L[Ly::DKP + a];
-      const float len = g * L[Ly::QPOS + act_qadr(a)], vel = g * L[Ly::QVEL + dof];
-      float f = kp * c + (-kp * len - tf(o + 6) * vel);
-      if (ti(o + 7)) f = fminf(fmaxf(f, tf(o + 8)), tf(o + 9));
+      const int a = lane;
+      float c = P.c;
+      if (P.clim) c = fminf(fmaxf(c, P.clo), P.chi);
+      const float g = P.g, kp = P.kp;
+      const float len = g * P.qp, vel = g * P.qd;
+      float f = kp * c + (-kp * len - P.kv * vel);
+      if (P.flim) f = fminf(fmaxf(f, P.flo), P.fhi);
       L[Ly::AF + a] = f;
-      L[Ly::FSM + dof] += g * f;
+      L[Ly::FSM + P.dof] += g * f;
     }
     TSYNC();
   }
@@ -1515,14 +1625,47 @@ struct TPhys {
 
   // plane floor vs hull for both feet at once (mjx collision_convex.plane_convex): lanes 0-7 take
   // the first floor pair, 8-15 the second
-  static DK void collide_planes(LP L, int lane) {
+  // collide_planes' words that the stages between kinematics and the collision do not write, a prologue
+  // that may run ahead of the stage before the collision:
+  //   gm, gpos, hv  the foot geom's frame in its body and the lane's hull vertices: words of the model
+  //                 table (never written after the launch's table copy)
+  //   R, xp         XMAT / XPOS of the foot's body: written by kinematics only
+  static constexpr int HVR = (Md::NHV + 7) / 8;  // hull vertices per lane (8 lanes per foot)
+  struct ColPre {
+    float R[9], xp[3], gm[9], gpos[3], hv[HVR][3];
+  };
+  static DK ColPre col_pre(LP L, int lane) {
+    ColPre P;
+    if constexpr (Md::FLOOR_TYPE != 1) {
+      const int h = lane >> 3, sub = lane & 7;
+      // (the foot's geom slot selected from the two compile-time entries: indexed by the lane's pair, the
+      // pair table is read from global memory)
+      constexpr int gs0 = cgeom_slot<Md>(Md::pair_geom2[Md::PLANE_PAIR[0]]);
+      constexpr int gs1 = cgeom_slot<Md>(Md::pair_geom2[Md::PLANE_PAIR[1]]);
+      const int gs = h == 0 ? gs0 : gs1;
+      const int o = Md::B_CGEOM + 16 * gs, b = ti(o);
+      for (int k = 0; k < 9; k++) { P.R[k] = L[Ly::XMAT + Ly::XMS * b + k]; P.gm[k] = tf(o + 4 + k); }
+      for (int k = 0; k < 3; k++) { P.gpos[k] = tf(o + 1 + k); P.xp[k] = L[Ly::XPOS + Ly::XPS * b + k]; }
+      for (int r = 0; r < HVR; r++) {
+        const int k = sub + 8 * r, kc = k < Md::NHV ? k : 0;  // (unmasked loads: vertices past the hull read vertex 0)
+        for (int q = 0; q < 3; q++) P.hv[r][q] = tf(Md::B_HULL + 3 * kc + q);
+      }
+    }
+    return P;
+  }
+  static DK void collide_planes(LP L, int lane, const ColPre& P) {
     constexpr int NH = Md::NHV;
     const int h = lane >> 3, sub = lane & 7;
     const int p = Md::PLANE_PAIR[0] * (1 - h) + Md::PLANE_PAIR[1] * h;
-    const int gs = cgeom_slot<Md>(Md::pair_geom2[p]);
     float pp[3], PR[9], cp[3], CR[9];
     Ph::geom_frame(L, 0, pp, PR);
-    cgeom_frame(L, gs, cp, CR);
+    {
+      // (cgeom_frame from the prologue's words)
+      float t[3];
+      mulmv3(t, P.R, P.gpos);
+      for (int k = 0; k < 3; k++) cp[k] = P.xp[k] + t[k];
+      mulmm3(CR, P.R, P.gm);
+    }
     const float n[3] = {PR[2], PR[5], PR[8]};
     const float dif[3] = {pp[0] - cp[0], pp[1] - cp[1], pp[2] - cp[2]};
     float pl[3], nl[3];
@@ -1530,13 +1673,13 @@ struct TPhys {
     mulmtv3(nl, CR, n);
     auto HVf = [&](int k, int q) { return tf(Md::B_HULL + 3 * k + q); };
     // this lane's vertices: k = sub + 8r
-    constexpr int R = (NH + 7) / 8;
+    constexpr int R = HVR;
     float sup[R], vx[R], vy[R], vz[R];
     float smax = -1e30f;
     for (int r = 0; r < R; r++) {
       const int k = sub + 8 * r;
       const bool ok = k < NH;
-      vx[r] = ok ? HVf(k, 0) : 0.0f; vy[r] = ok ? HVf(k, 1) : 0.0f; vz[r] = ok ? HVf(k, 2) : 0.0f;
+      vx[r] = ok ? P.hv[r][0] : 0.0f; vy[r] = ok ? P.hv[r][1] : 0.0f; vz[r] = ok ? P.hv[r][2] : 0.0f;
       sup[r] = ok ? (pl[0] - vx[r]) * nl[0] + (pl[1] - vy[r]) * nl[1] + (pl[2] - vz[r]) * nl[2] : -1e30f;
       smax = fmaxf(smax, sup[r]);
     }
@@ -2770,10 +2913,10 @@ struct TPhys {
     collide_hulls_team(L, lane, 4 * p, p1, R1, p2, R2, cc);
   }
 
-  static DK void collision(LP L, int lane, const float* hf) {
+  static DK void collision(LP L, int lane, const float* hf, const ColPre& P) {
     STAGE_T0();
     if constexpr (Md::FLOOR_TYPE == 1) collide_hfield(L, lane, hf);
-    else collide_planes(L, lane);
+    else collide_planes(L, lane, P);
     STAGE_MARK(ST_COLLISION_FLOOR);
     if (Md::FOOT_PAIR >= 0) {
       constexpr int p = Md::FOOT_PAIR;
@@ -2849,23 +2992,39 @@ struct TPhys {
   }
 
   // J.x of one contact slot (4 pyramid edges) for body spatial motions SL/SR (runtime pair)
+  // the slot's words contact_jx reads: the pair's geoms and friction (words of the model table, never
+  // written after the launch's table copy) and the contact's arm and frame (CR, CFR: written by the
+  // collision stage only), so a solver stage may load them ahead of the sync that precedes its use of them
+  struct JxIn {
+    int s1, s2;
+    float mu, r[3], fr[9];
+  };
+  static DK JxIn jx_load(LP L, int p, int slot) {
+    const int o = Md::B_PAIR + PAIRW * p;
+    JxIn J;
+    J.s1 = ti(o); J.s2 = ti(o + 1); J.mu = tf(o + 2);
+    for (int k = 0; k < 3; k++) J.r[k] = L[Ly::CR + Ly::CRS * slot + k];
+    for (int k = 0; k < 9; k++) J.fr[k] = L[Ly::CFR + Ly::CFS * slot + k];
+    return J;
+  }
   static DK void contact_jx(LP L, int p, int slot, const float* SL, const float* SR, float* out4) {
+    contact_jx(jx_load(L, p, slot), SL, SR, out4);
+  }
+  static DK void contact_jx(const JxIn& J, const float* SL, const float* SR, float* out4) {
     // contractions within expressions only: this function's statements are inlined into the fused warm
     // start of step_kernel and into the split halves of the latency kernels, where the backend formed
     // different FMAs across them (the flat scenes' kernels then agreed only to fp32 rounding;
     // tools/fpc_bisect.py located it, profiles/r05_lat_bitcmp.txt). With it the kernels agree bit for bit.
 #pragma clang fp contract(on)
-    const int o = Md::B_PAIR + PAIRW * p;
-    const int s1 = ti(o), s2 = ti(o + 1);
-    const float mu = tf(o + 2);
-    const float r[3] = {L[Ly::CR + Ly::CRS * slot], L[Ly::CR + Ly::CRS * slot + 1], L[Ly::CR + Ly::CRS * slot + 2]};
+    const int s1 = J.s1, s2 = J.s2;
+    const float mu = J.mu;
+    const float r[3] = {J.r[0], J.r[1], J.r[2]};
     float v[3] = {0.0f, 0.0f, 0.0f}, t[3];
     if (s2 != 0) { Ph::contact_vel(s2 == 1 ? SL : SR, r, t); v[0] += t[0]; v[1] += t[1]; v[2] += t[2]; }
     if (s1 != 0) { Ph::contact_vel(s1 == 1 ? SL : SR, r, t); v[0] -= t[0]; v[1] -= t[1]; v[2] -= t[2]; }
     float jr[3];
     for (int q = 0; q < 3; q++)
-      jr[q] = L[Ly::CFR + Ly::CFS * slot + 3 * q] * v[0] + L[Ly::CFR + Ly::CFS * slot + 3 * q + 1] * v[1] +
-              L[Ly::CFR + Ly::CFS * slot + 3 * q + 2] * v[2];
+      jr[q] = J.fr[3 * q] * v[0] + J.fr[3 * q + 1] * v[1] + J.fr[3 * q + 2] * v[2];
     out4[0] = jr[0] + mu * jr[1];
     out4[1] = jr[0] - mu * jr[1];
     out4[2] = jr[0] + mu * jr[2];
@@ -2899,26 +3058,34 @@ struct TPhys {
       asm volatile("" : "+v"(lo));
       const bool left = lo < 6;
       const int k = left ? lo : lo - 6;
+      // every chain position's words first, then the sums: position by position the step kernel waited
+      // for each position's loads by themselves (an LDS round trip per position)
+      float cvs[Md::MAXCHAIN], xs[Md::MAXCHAIN], x2s[Md::MAXCHAIN];
+#pragma unroll
+      for (int c = 0; c < Md::MAXCHAIN; c++) {
+        const int iL = Md::chain[Md::LFOOT_BODY][c], iR = Md::chain[Md::RFOOT_BODY][c];
+        cvs[c] = xs[c] = x2s[c] = 0.0f;
+        if (iL < 0 && iR < 0) continue;
+        const bool unit = FREE0 && iL == iR && iL >= 0 && iL < 3;
+        const int ic = unit ? iL : (left ? (iL >= 0 ? iL : 0) : (iR >= 0 ? iR : 0));
+        if (!unit) cvs[c] = L[Ly::CDOF + 6 * ic + k];
+        xs[c] = L[X + ic];
+        if (X2 >= 0) x2s[c] = L[X2 + ic];
+      }
       float s = 0.0f, s2 = 0.0f;
 #pragma unroll
       for (int c = 0; c < Md::MAXCHAIN; c++) {
         const int iL = Md::chain[Md::LFOOT_BODY][c], iR = Md::chain[Md::RFOOT_BODY][c];
         if (iL < 0 && iR < 0) continue;
         const bool ok = left ? iL >= 0 : iR >= 0;
-        const int ic = left ? (iL >= 0 ? iL : 0) : (iR >= 0 ? iR : 0);
         if (FREE0 && iL == iR && iL >= 0 && iL < 3) {  // cdof = e_{3+i}: only lane k = 3 + i adds x
-          const float x = L[X + iL];
-          s += k == 3 + iL ? x : 0.0f;
-          if (X2 >= 0) {
-            const float x2 = L[X2 + iL];
-            s2 += k == 3 + iL ? x2 : 0.0f;
-          }
+          s += k == 3 + iL ? xs[c] : 0.0f;
+          if (X2 >= 0) s2 += k == 3 + iL ? x2s[c] : 0.0f;
           continue;
         }
-        const float cv = L[Ly::CDOF + 6 * ic + k];
-        const float cd = ok ? cv : 0.0f;
-        s += cd * L[X + ic];
-        if (X2 >= 0) s2 += cd * L[X2 + ic];
+        const float cd = ok ? cvs[c] : 0.0f;
+        s += cd * xs[c];
+        if (X2 >= 0) s2 += cd * x2s[c];
       }
       so = s;
       so2 = s2;
@@ -3084,6 +3251,38 @@ struct TPhys {
   // warm start vs smooth acceleration (mjx solver.solve's start): returns the Gauss cost at the start
   static DK float warm_start(LP L, int lane, const float (*Mc)[NV]) {
     STAGE_T0();
+    // the words of the rows' costs that the products below do not write (they write MA), read here, ahead
+    // of the products and their sync, whose work covers the round trip:
+    //   fD, lD, cD, far, lar, car, lsg  RD, AREF, LSGN: written by make_rows only
+    //   ff                              per-env model value (DFRIC: constant through the launch)
+    //   fw, lw, w                       WARM: written by euler() and the env code only
+    //   fq, lq, q                       QSM: written by smooth_acc, which ends with a sync of its own
+    //   fsm                             FSM: written by rne and smooth
+    //   jx                              see JxIn
+    struct WarmPre {
+      float fD, ff, far, fw, fq, lD[NLR], lsg[NLR], lar[NLR], lw[NLR], lq[NLR], cD[4], car[4];
+      float fsm[NC], w[NC], q[NC];
+      JxIn jx;
+    } P;
+    {
+      const int r = lane < NFRIC ? lane : 0, i = fric_dof(r);
+      P.fD = L[Ly::RD + r]; P.ff = L[Ly::DFRIC + i]; P.far = L[Ly::AREF + r];
+      P.fw = L[Ly::WARM + i]; P.fq = L[Ly::QSM + i];
+#pragma unroll
+      for (int m = 0; m < NLR; m++) {
+        const int rl = lane + TEAM * m, rc = rl < NLIM ? rl : 0, il = lim_dof(rc);
+        P.lD[m] = L[Ly::RD + R_LIM + rc]; P.lsg[m] = L[Ly::LSGN + rc]; P.lar[m] = L[Ly::AREF + R_LIM + rc];
+        P.lw[m] = L[Ly::WARM + il]; P.lq[m] = L[Ly::QSM + il];
+      }
+      const int slot = lane < NCON ? lane : 0;
+      P.jx = jx_load(L, slot >> 2, slot);
+      for (int e = 0; e < 4; e++) { P.cD[e] = L[Ly::RD + R_CON + 4 * slot + e]; P.car[e] = L[Ly::AREF + R_CON + 4 * slot + e]; }
+#pragma unroll
+      for (int s = 0; s < NC; s++) {
+        const int c = TEAM * s + lane, cc = c < NV ? c : 0;
+        P.fsm[s] = L[Ly::FSM + cc]; P.w[s] = L[Ly::WARM + cc]; P.q[s] = L[Ly::QSM + cc];
+      }
+    }
     // warm start vs smooth acceleration: J and M products of both in one pass
     // (M qacc_smooth = qfrc_smooth by definition: no product needed for the smooth start)
     float sw, ss;
@@ -3103,30 +3302,33 @@ struct TPhys {
     {
       // branchless (no lane-divergent region: see TL::SINK)
       const bool fr = lane < NFRIC;
-      const int r = fr ? lane : 0, i = fric_dof(r);
-      const float D = L[Ly::RD + r], f = L[Ly::DFRIC + i], ar = L[Ly::AREF + r];
-      const float jw = L[Ly::WARM + i] - ar, js = L[Ly::QSM + i] - ar;
+      const int r = fr ? lane : 0;
+      const float D = P.fD, f = P.ff, ar = P.far;
+      const float jw = P.fw - ar, js = P.fq - ar;
       cwp += fr ? fric_cost(D, jw, f) : 0.0f;
       csp += fr ? fric_cost(D, js, f) : 0.0f;
       L[fr ? Ly::JA + r : TL::SINK + lane] = jw;
       L[fr ? Ly::JV + r : TL::SINK + TEAM + lane] = js;
     }
-    team_for<NLIM>(lane, [&](int r) {
-      const int i = lim_dof(r), row = R_LIM + r;
-      const float D = L[Ly::RD + row], sg = L[Ly::LSGN + r], ar = L[Ly::AREF + row];
-      const float jw = sg * L[Ly::WARM + i] - ar, js = sg * L[Ly::QSM + i] - ar;
+#pragma unroll
+    for (int m = 0; m < NLR; m++) {
+      const int r = lane + TEAM * m;
+      if (NLIM % TEAM != 0 && m == NLR - 1 && r >= NLIM) continue;
+      const int row = R_LIM + r;
+      const float D = P.lD[m], sg = P.lsg[m], ar = P.lar[m];
+      const float jw = sg * P.lw[m] - ar, js = sg * P.lq[m] - ar;
       cwp += jw < 0.0f ? 0.5f * D * jw * jw : 0.0f;
       csp += js < 0.0f ? 0.5f * D * js * js : 0.0f;
       L[Ly::JA + row] = jw;
       L[Ly::JV + row] = js;
-    });
+    }
     if (lane < NCON) {
       float vw[4], vs[4];
-      contact_jx(L, lane >> 2, lane, SL, SR, vw);
-      contact_jx(L, lane >> 2, lane, SL2, SR2, vs);
+      contact_jx(P.jx, SL, SR, vw);
+      contact_jx(P.jx, SL2, SR2, vs);
       for (int e = 0; e < 4; e++) {
         const int row = R_CON + 4 * lane + e;
-        const float D = L[Ly::RD + row], ar = L[Ly::AREF + row];
+        const float D = P.cD[e], ar = P.car[e];
         const float jw = vw[e] - ar, js = vs[e] - ar;
         cwp += jw < 0.0f ? 0.5f * D * jw * jw : 0.0f;
         csp += js < 0.0f ? 0.5f * D * js * js : 0.0f;
@@ -3134,7 +3336,12 @@ struct TPhys {
         L[Ly::JV + row] = js;
       }
     }
-    team_for<NV>(lane, [&](int i) { gwp += 0.5f * (L[Ly::MA + i] - L[Ly::FSM + i]) * (L[Ly::WARM + i] - L[Ly::QSM + i]); });
+#pragma unroll
+    for (int s = 0; s < NC; s++) {
+      const int i = TEAM * s + lane;
+      if (NV % TEAM != 0 && s == NC - 1 && i >= NV) continue;
+      gwp += 0.5f * (L[Ly::MA + i] - P.fsm[s]) * (P.w[s] - P.q[s]);
+    }
     const float gw = tsum(gwp);
     const float cw = gw + tsum(cwp), cs = tsum(csp);
     float g0;
@@ -3177,6 +3384,35 @@ struct TPhys {
       newton_dense(L, lane);  // rare: foot/foot contact rows active (dense H)
       TSYNC();
     }
+    // the rows' words of the line search that neither the direction nor M.search touch, read here, ahead
+    // of the products and their sync, whose work covers the round trip (the index -> row chains too):
+    //   fD, lD, cD, lsg  RD, LSGN: written by make_rows only
+    //   fja, lja, cja    JA: written by the warm start (and, after a line search, behind a sync of its own)
+    //   ff               per-env model value (DFRIC: constant through the launch)
+    //   jx               see JxIn
+    //   ma, fsm          MA: written by the warm start and after a line search; FSM: by rne and smooth
+    // (the direction writes SRCH, the products GRAD: both are read after the sync)
+    struct SearchPre {
+      float fD, fja, ff, lD[NLR], lja[NLR], lsg[NLR], cD[4], cja[4], ma[NC], fsm[NC];
+      JxIn jx;
+    } SP;
+    {
+      const int slot = lane < NCON ? lane : 0;
+      SP.jx = jx_load(L, slot >> 2, slot);
+      const int r = lane < NFRIC ? lane : 0;
+      SP.fD = L[Ly::RD + r]; SP.fja = L[Ly::JA + r]; SP.ff = L[Ly::DFRIC + fric_dof(r)];
+#pragma unroll
+      for (int m = 0; m < NLR; m++) {
+        const int rl = lane + TEAM * m, rc = rl < NLIM ? rl : 0;
+        SP.lD[m] = L[Ly::RD + R_LIM + rc]; SP.lja[m] = L[Ly::JA + R_LIM + rc]; SP.lsg[m] = L[Ly::LSGN + rc];
+      }
+      for (int e = 0; e < 4; e++) { SP.cD[e] = L[Ly::RD + R_CON + 4 * slot + e]; SP.cja[e] = L[Ly::JA + R_CON + 4 * slot + e]; }
+#pragma unroll
+      for (int s = 0; s < NC; s++) {
+        const int c = TEAM * s + lane, cc = c < NV ? c : 0;
+        SP.ma[s] = L[Ly::MA + cc]; SP.fsm[s] = L[Ly::FSM + cc];
+      }
+    }
     // J.search and M.search in one pass; rows go straight to registers
     float sv, sv2;
     spatial2(L, lane, Ly::SRCH, -1, sv, sv2);
@@ -3190,38 +3426,39 @@ struct TPhys {
     {
       const bool fr = lane < NFRIC;
       const int r = fr ? lane : 0, i = fric_dof(r);
-      const float D = L[Ly::RD + r], ja = L[Ly::JA + r], v = L[Ly::SRCH + i], f = L[Ly::DFRIC + i];
+      const float D = SP.fD, ja = SP.fja, v = L[Ly::SRCH + i], f = SP.ff;
       set_fric(R, fr ? D : 1.0f, fr ? ja : 0.0f, fr ? v : 0.0f, fr ? f : 0.0f);
     }
 #pragma unroll
     for (int m = 0; m < NLR; m++) {
       const int r = lane + TEAM * m;
       const bool ok = r < NLIM;
-      const int rc = ok ? r : 0, i = lim_dof(rc), row = R_LIM + rc;
-      const float D = L[Ly::RD + row], ja = L[Ly::JA + row], v = L[Ly::LSGN + rc] * L[Ly::SRCH + i];
+      const int rc = ok ? r : 0, i = lim_dof(rc);
+      const float D = SP.lD[m], ja = SP.lja[m], v = SP.lsg[m] * L[Ly::SRCH + i];
       set_row(R, m, ok ? D : 0.0f, ok ? ja : 0.0f, ok ? v : 0.0f);
     }
     {
       float SL[6], SR[6], v[4];
-      const int slot = lane < NCON ? lane : 0;
       sp_bcast(sv, SL, SR);
-      contact_jx(L, slot >> 2, slot, SL, SR, v);
+      contact_jx(SP.jx, SL, SR, v);
       for (int e = 0; e < 4; e++) {
-        const int row = R_CON + 4 * slot + e;
         const bool ok = lane < NCON;
-        const float D = L[Ly::RD + row], ja = L[Ly::JA + row];
+        const float D = SP.cD[e], ja = SP.cja[e];
         set_row(R, NLR + e, ok ? D : 0.0f, ok ? ja : 0.0f, ok ? v[e] : 0.0f);
       }
     }
     float sn = 0.0f, sMa = 0.0f, sf = 0.0f, sMv = 0.0f;
     LS_DUMP_START(L, lane);
-    team_for<NV>(lane, [&](int i) {
+#pragma unroll
+    for (int s = 0; s < NC; s++) {
+      const int i = TEAM * s + lane;
+      if (NV % TEAM != 0 && s == NC - 1 && i >= NV) continue;
       const float sv = L[Ly::SRCH + i];
       sn += sv * sv;
-      sMa += sv * L[Ly::MA + i];
-      sf += sv * L[Ly::FSM + i];
+      sMa += sv * SP.ma[s];
+      sf += sv * SP.fsm[s];
       sMv += sv * L[Ly::GRAD + i];
-    });
+    }
     LS_DUMP_NORM(L, lane, sn);
     sn = tsum(sn); sMa = tsum(sMa); sf = tsum(sf); sMv = tsum(sMv);
     STAGE_MARK(ST_SEARCH_PRODUCTS);
@@ -3423,25 +3660,32 @@ struct TPhys {
   static DK void step(LP L, int lane, bool integrate, bool want_out, float* aux, int aux_stride, float* scratch,
                       int sstride, const float* hf) {
     STAGE_T0();
+    // each stage's prologue (the words it may read before the stage ahead of it has finished) is issued ahead
+    // of that stage, whose work then covers the round trip
+    const ComPre cp = com_pre(L, lane);
     kinematics(L, lane);
     STAGE_AGAIN(6, kinematics(L, lane));
     STAGE_MARK(ST_KINEMATICS);
-    com_pos(L, lane);
-    STAGE_AGAIN(7, com_pos(L, lane));
+    const RnePre rp = rne_pre(L, lane);
+    com_pos(L, lane, cp);
+    STAGE_AGAIN(7, com_pos(L, lane, cp));
     STAGE_MARK(ST_COM_POS);
-    rne(L, lane);
+    rne(L, lane, rp);
     STAGE_MARK(ST_RNE);
+    // smooth's inputs do not depend on crb: issued here, their round trip is covered by crb's work
+    const SmoothPre sp = smooth_pre(L, lane);
     crb(L, lane);
     STAGE_AGAIN(1, crb(L, lane));
     STAGE_MARK(ST_CRB);
-    smooth(L, lane);
-    STAGE_AGAIN(8, rne(L, lane));  // (smooth adds to rne's qfrc_smooth: the pair is idempotent, smooth alone is not)
-    STAGE_AGAIN(8, smooth(L, lane));
+    const ColPre lp = col_pre(L, lane);
+    smooth(L, lane, sp);
+    STAGE_AGAIN(8, rne(L, lane, rp));  // (smooth adds to rne's qfrc_smooth: the pair is idempotent, smooth alone is not)
+    STAGE_AGAIN(8, smooth(L, lane, smooth_pre(L, lane)));
     STAGE_MARK(ST_SMOOTH);
     // collision and the constraint rows depend on the kinematics only: they run before the
     // smooth acceleration so that M is loaded into registers once for both solves
-    collision(L, lane, hf);
-    STAGE_AGAIN(2, collision(L, lane, hf));
+    collision(L, lane, hf, lp);
+    STAGE_AGAIN(2, collision(L, lane, hf, lp));
     STAGE_MARK(ST_COLLISION);
     make_rows(L, lane);
     STAGE_AGAIN(3, make_rows(L, lane));
@@ -3527,14 +3771,14 @@ struct TPhys {
     ev_wait(EV_EULER, s);
     LAT_T(0, s);
     kinematics(L, lane);
-    com_pos(L, lane);
+    com_pos(L, lane, com_pre(L, lane));
     ev_signal(EV_KIN, s + 1);
     LAT_T(1, s);
-    rne_vel(L, lane);
+    rne_vel(L, lane, rne_pre(L, lane));
     ev_signal(EV_VEL, s + 1);
     LAT_T(2, s);
     rne_rest<1>(L, lane);
-    smooth(L, lane);
+    smooth(L, lane, smooth_pre(L, lane));
     ev_signal(EV_FSM, s + 1);
     LAT_T(3, s);
   }
@@ -3589,7 +3833,7 @@ struct TPhys {
   static DK void lat_r2(LP L, int lane, int s, const float* hf) {
     ev_wait(EV_KIN, s + 1);
     LAT_T(20, s);
-    collision(L, lane, hf);
+    collision(L, lane, hf, col_pre(L, lane));
     LAT_T(21, s);
     ev_wait(EV_VEL, s + 1);
     LAT_T(22, s);
@@ -3635,16 +3879,16 @@ struct TPhys {
     ev_wait(EV_EULER, s);
     LAT2_T(0, s);
     kinematics(L, lane);
-    com_pos(L, lane);
+    com_pos(L, lane, com_pre(L, lane));
     ev_signal(EV_KIN, s + 1);
     LAT2_T(1, s);
-    rne_vel(L, lane);
+    rne_vel(L, lane, rne_pre(L, lane));
     LAT2_T(2, s);
     rne_rest<1>(L, lane);
-    smooth(L, lane);
+    smooth(L, lane, smooth_pre(L, lane));
     ev_signal(EV_FSM, s + 1);
     LAT2_T(3, s);
-    collision(L, lane, hf);
+    collision(L, lane, hf, col_pre(L, lane));
     LAT2_T(4, s);
     make_rows(L, lane);
     ev_signal(EV_ROWS, s + 1);
