@@ -1,0 +1,101 @@
+/* duck_fleet.h — C ABI of the batched deployment loop (sim2sim.FleetInfer; libduck.so and every
+ * model's own library).
+ *
+ * The reference decides whether an exported policy goes on the robot by running it in its deployment
+ * control loop (playground/open_duck_mini_v2/mujoco_infer.py:156-241 on mujoco_infer_base.py), which is
+ * not the training env: +1.3 on the accelerometer's x, a motor-speed limit, no action delay, noise or
+ * pushes. One control period of that loop for N robots is four launches on one stream:
+ *
+ *   duck_physics_step   mj_step x decimation (mujoco_infer.py:170-174), 10 substeps, with `aux`
+ *   duck_fleet_observe  the phase advance and get_obs (mujoco_infer.py:175-197, :67-103), plus the
+ *                       per-robot bookkeeping of an evaluation (brax EvalWrapper's rule, as
+ *                       duck_episode_accumulate(EVAL) applies it)
+ *   duck_policy_act     self.policy.infer(obs) (mujoco_infer.py:203; duck_ppo.h)
+ *   duck_fleet_actuate  the action history, motor targets, speed limit and ctrl (mujoco_infer.py:208-231)
+ *
+ * Both entries are model-agnostic: a host descriptor filled from the compiled model tells them where
+ * the sensors, the actuated joints and the foot contacts are. Conventions are duck.h's: DEVICE
+ * pointers, float32, no allocation, no synchronisation, work ordered on `stream`, negative codes with
+ * duck_last_error(), DUCK_EINVAL on null pointers and bad sizes.
+ *
+ * Arithmetic: every value written is one fp32 operation on loaded words (no contraction into fma), so a
+ * float32 restatement reproduces it bit for bit. The library runs with fp32 denormals flushed to zero.
+ */
+#ifndef DUCK_FLEET_H_
+#define DUCK_FLEET_H_
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define DUCK_FLEET_MAX_NU 16
+
+typedef struct {
+  int nq, nv, nu;        /* nu <= DUCK_FLEET_MAX_NU */
+  int naux;              /* rows of the aux record (duck_aux_size) */
+  int sens_off, con_off; /* first aux row of sensordata and of con_dist (write_aux's order:
+                            qacc, qacc_smooth, qvel, qfrc_smooth [nv each], actuator_force [nu], sensordata, con_dist) */
+  int gyro, accelerometer, upvector, local_linvel; /* sensor_adr of each (3 values) inside sensordata */
+  int act_qpos[DUCK_FLEET_MAX_NU];      /* jnt_qposadr of each actuator's joint */
+  int act_dof[DUCK_FLEET_MAX_NU];       /* jnt_dofadr of each actuator's joint */
+  float act_default[DUCK_FLEET_MAX_NU]; /* the home keyframe's ctrl (default_actuator, mujoco_infer_base.py) */
+  int foot_con[2];        /* first of the 4 con_dist slots of the (floor, left foot) and (floor, right foot) pairs */
+  float dof_vel_scale;    /* 0.05  (mujoco_infer.py:30) */
+  float action_scale;     /* 0.25  (mujoco_infer.py:31) */
+  float accel_x_offset;   /* 1.3   (mujoco_infer.py:74) */
+  float target_step;      /* float32(5.24 * 0.002 * 10): max_motor_velocity * sim_dt * decimation (mujoco_infer.py:58, :216-225) */
+  int nb_steps_in_period; /* PolyReferenceMotion.nb_steps_in_period (>= 1 unless standing) */
+  int standing;           /* mujoco_infer.py:175: the phase is not advanced */
+  int speed_limits;       /* USE_MOTOR_SPEED_LIMITS (mujoco_infer.py:14) */
+} duck_fleet_desc;
+
+/* Per-robot control record ctl [N][C], row-major, C = DUCK_FLEET_CTL_SIZE(nu) floats:
+ *   [0, nu)        last_action
+ *   [nu, 2nu)      last_last_action
+ *   [2nu, 3nu)     last_last_last_action
+ *   [3nu, 4nu)     motor_targets
+ *   [4nu, 5nu)     prev_motor_targets
+ *   [5nu, 5nu+7)   command (lin_vel_x, lin_vel_y, ang_vel, neck_pitch, head_pitch, head_yaw, head_roll)
+ *   5nu+7          imitation_i
+ *   5nu+8          phase_frequency_factor
+ *   5nu+9, 5nu+10  imitation_phase (cos, sin)
+ * The reference starts with zero actions, both targets at default_actuator, a zero command, imitation_i 0,
+ * factor 1 and phase (0, 0) (mujoco_infer.py:49-60). */
+#define DUCK_FLEET_CTL_SIZE(nu) (5 * (nu) + 11)
+/* obs [N][DUCK_FLEET_OBS_SIZE(nu)] row-major; acc [N][DUCK_FLEET_ACC_SIZE] row-major */
+#define DUCK_FLEET_OBS_SIZE(nu) (17 + 6 * (nu))
+#define DUCK_FLEET_ACC_SIZE 6
+
+/* mujoco_infer.py:175-197 and :67-103 after a control period's physics. qpos [nq][N], qvel [nv][N] and
+ * aux [naux][N] are duck_physics_step's SoA buffers (aux of the period's last substep).
+ *
+ * Phase (unless desc.standing), fp32: i = fmodf(i + factor, nb); a = (i / nb) * float32(2 pi), the
+ * division correctly rounded; imitation_phase = (cosf(a), sinf(a)) with the accurate functions.
+ *
+ * obs row, the reference's order: gyro[3], accelerometer[3] (x + accel_x_offset), command[7],
+ * qpos[act_qpos[a]] - act_default[a], dof_vel_scale * qvel[act_dof[a]], last_action, last_last_action,
+ * last_last_last_action, motor_targets, the two foot contacts, imitation_phase. A foot contact is 1.0
+ * when any of the foot's four con_dist values is < 0, else 0.0 (NaN and +-0 are no contact;
+ * mujoco_infer_base.py:259-282).
+ *
+ * Bookkeeping. A robot is fallen when upvector[2] < 0 or any of its qpos or qvel is NaN (the training
+ * env's termination on the same sensor, joystick.py:483-485). While alive[e] != 0: if fallen, alive[e] = 0;
+ * otherwise acc[e][.] += {1, vx, vy, wz, (vx-cx)*(vx-cx) + (vy-cy)*(vy-cy), (wz-cz)*(wz-cz)} with
+ * v = local_linvel, w = gyro, c = command: plain fp32 adds in period order, every product and sum rounded
+ * on its own. A fallen robot is still observed and controlled (the reference loop never stops); only its
+ * accumulators stop. alive [N] float32, set to 1 by the caller. */
+int duck_fleet_observe(const duck_fleet_desc* desc, int N, const float* qpos, const float* qvel, const float* aux,
+                       float* ctl, float* obs, float* acc, float* alive, void* stream);
+
+/* mujoco_infer.py:208-231. action [N][nu] row-major (duck_policy_act's output). Shifts the three-deep
+ * action history, motor_targets = act_default + action * action_scale (product, then sum); when
+ * desc.speed_limits: motor_targets = min(max(motor_targets, prev - target_step), prev + target_step) (a NaN
+ * target stays NaN, as np.clip leaves it) and prev_motor_targets = motor_targets; then ctrl [nu][N] (SoA,
+ * the next duck_physics_step's input) = motor_targets. */
+int duck_fleet_actuate(const duck_fleet_desc* desc, int N, const float* action, float* ctl, float* ctrl,
+                       void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* DUCK_FLEET_H_ */

@@ -3,6 +3,7 @@
 // variant (variant_*.hip). Every entry returns DUCK_OK or a negative code with a
 // thread-local message; no entry allocates, synchronises or throws on the step path.
 #include "duck_common.h"
+#include "../../include/duck_fleet.h"
 #include "../../include/duck_ppo.h"
 
 // the compiled model variants of this library (codegen.variant_registry; generated/ for libduck.so,
@@ -88,6 +89,149 @@ __global__ __launch_bounds__(256) void episode_accumulate_kernel(int n, int nmet
     flag[e] += 1.f;
   }
 }
+
+// The deployment loop's host code on the device (include/duck_fleet.h): the observation, the action history,
+// the motor targets and an evaluation's bookkeeping for N robots, driven by a descriptor of the model instead
+// of a compiled variant, so they live in this unit and ship with every model's library. A 16-lane group
+// takes a robot: its lanes read the SoA rows next to the neighbouring groups' (64-byte segments) and write 16
+// consecutive words of the robot's row. Lanes past the last robot run on robot n - 1 with their stores
+// masked, so that the group votes below see whole waves.
+constexpr int FLEET_TEAM = 16;
+constexpr int FLEET_TPB = 256;
+
+// x / y correctly rounded for normal x, y and quotient (this library is compiled with approximate fp32
+// division): a Newton step on v_rcp, then the quotient's residual
+__device__ __forceinline__ float fleet_div_rn(float x, float y) {
+  float r = __builtin_amdgcn_rcpf(y);
+  r = fmaf(fmaf(-y, r, 1.f), r, r);
+  const float q = x * r;
+  return fmaf(fmaf(-q, y, x), r, q);
+}
+
+__global__ __launch_bounds__(FLEET_TPB) void fleet_observe_kernel(const duck_fleet_desc D, int n,
+                                                                  const float* __restrict__ qpos,
+                                                                  const float* __restrict__ qvel,
+                                                                  const float* __restrict__ aux, float* ctl,
+                                                                  float* __restrict__ obs, float* __restrict__ acc,
+                                                                  float* __restrict__ alive) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x % FLEET_TEAM;
+  const int e0 = blockIdx.x * (FLEET_TPB / FLEET_TEAM) + threadIdx.x / FLEET_TEAM;
+  const bool on = e0 < n;
+  const size_t e = on ? e0 : n - 1, N = n;
+  const int shift = (threadIdx.x % 64) / FLEET_TEAM * FLEET_TEAM;  // this group's bits of a wave vote
+  const int nu = D.nu, C = DUCK_FLEET_CTL_SIZE(nu), O = DUCK_FLEET_OBS_SIZE(nu);
+  float* c = ctl + e * C;
+  const float* sens = aux + (size_t)D.sens_off * N + e;
+
+  // mujoco_infer.py:175-197
+  float ii = c[5 * nu + 7], ph0 = c[5 * nu + 9], ph1 = c[5 * nu + 10];
+  if (!D.standing) {
+    const float nb = (float)D.nb_steps_in_period;
+    ii = fmodf(ii + c[5 * nu + 8], nb);
+    const float a = fleet_div_rn(ii, nb) * 6.2831855f;
+    ph0 = cosf(a);
+    ph1 = sinf(a);
+  }
+
+  // the feet: lanes 0-3 the left foot's four contact slots, 4-7 the right foot's
+  bool pen = false;
+  if (lane < 8) pen = aux[(size_t)(D.con_off + D.foot_con[lane / 4] + lane % 4) * N + e] < 0.f;
+  const unsigned feet = (unsigned)(__ballot(pen) >> shift) & 0xffu;
+  // a NaN anywhere in the state (joystick.py:483-485)
+  bool bad = false;
+  for (int k = lane; k < D.nq + D.nv; k += FLEET_TEAM) {
+    const float v = k < D.nq ? qpos[(size_t)k * N + e] : qvel[(size_t)(k - D.nq) * N + e];
+    bad |= v != v;
+  }
+  const bool nan_state = ((unsigned)(__ballot(bad) >> shift) & 0xffffu) != 0;
+
+  // mujoco_infer.py:67-103, one column per lane and pass
+  for (int k = lane; k < O; k += FLEET_TEAM) {
+    float v;
+    int j = k;
+    if (j < 3) {
+      v = sens[(size_t)(D.gyro + j) * N];
+    } else if ((j -= 3) < 3) {
+      v = sens[(size_t)(D.accelerometer + j) * N];
+      if (j == 0) v = v + D.accel_x_offset;
+    } else if ((j -= 3) < 7) {
+      v = c[5 * nu + j];
+    } else if ((j -= 7) < nu) {
+      v = qpos[(size_t)D.act_qpos[j] * N + e] - D.act_default[j];
+    } else if ((j -= nu) < nu) {
+      v = qvel[(size_t)D.act_dof[j] * N + e] * D.dof_vel_scale;
+    } else if ((j -= nu) < 4 * nu) {
+      v = c[j];  // the three past actions, then the motor targets: the record's order
+    } else if ((j -= 4 * nu) < 2) {
+      v = ((feet >> (4 * j)) & 0xfu) ? 1.f : 0.f;
+    } else {
+      v = j == 2 ? ph0 : ph1;
+    }
+    if (on) obs[e * O + k] = v;
+  }
+
+  if (on && lane == 0) {
+    if (alive[e] != 0.f) {
+      const float vx = sens[(size_t)D.local_linvel * N], vy = sens[(size_t)(D.local_linvel + 1) * N];
+      const float wz = sens[(size_t)(D.gyro + 2) * N];
+      if (nan_state || sens[(size_t)(D.upvector + 2) * N] < 0.f) {
+        alive[e] = 0.f;
+      } else {
+        float* r = acc + e * DUCK_FLEET_ACC_SIZE;
+        const float dx = vx - c[5 * nu], dy = vy - c[5 * nu + 1], dz = wz - c[5 * nu + 2];
+        const float dx2 = dx * dx, dy2 = dy * dy;
+        r[0] += 1.f;
+        r[1] += vx;
+        r[2] += vy;
+        r[3] += wz;
+        r[4] += dx2 + dy2;
+        r[5] += dz * dz;
+      }
+    }
+    if (!D.standing) {
+      c[5 * nu + 7] = ii;
+      c[5 * nu + 9] = ph0;
+      c[5 * nu + 10] = ph1;
+    }
+  }
+}
+
+// mujoco_infer.py:208-231, one lane per (robot, actuator)
+__global__ __launch_bounds__(FLEET_TPB) void fleet_actuate_kernel(const duck_fleet_desc D, int n,
+                                                                  const float* __restrict__ action, float* ctl,
+                                                                  float* __restrict__ ctrl) {
+#pragma clang fp contract(off)
+  const int a = threadIdx.x % FLEET_TEAM;
+  const int e0 = blockIdx.x * (FLEET_TPB / FLEET_TEAM) + threadIdx.x / FLEET_TEAM;
+  const int nu = D.nu;
+  if (e0 >= n || a >= nu) return;
+  const size_t e = e0;
+  float* c = ctl + e * DUCK_FLEET_CTL_SIZE(nu);
+  const float act = action[e * nu + a], last = c[a], last_last = c[nu + a];
+  c[2 * nu + a] = last_last;
+  c[nu + a] = last;
+  c[a] = act;
+  const float scaled = act * D.action_scale;
+  float mt = D.act_default[a] + scaled;
+  if (D.speed_limits) {
+    const float prev = c[4 * nu + a];
+    const float lo = prev - D.target_step, hi = prev + D.target_step;
+    mt = mt < lo ? lo : mt;  // np.clip: a NaN target stays NaN
+    mt = mt > hi ? hi : mt;
+    c[4 * nu + a] = mt;
+  }
+  c[3 * nu + a] = mt;
+  ctrl[(size_t)a * n + e] = mt;
+}
+
+static const char* fleet_desc_error(const duck_fleet_desc* d) {
+  if (d->nq < 1 || d->nv < 1 || d->nu < 1 || d->nu > DUCK_FLEET_MAX_NU) return "nq, nv >= 1 and 1 <= nu <= 16";
+  for (int a = 0; a < d->nu; a++)
+    if (d->act_qpos[a] < 0 || d->act_qpos[a] >= d->nq || d->act_dof[a] < 0 || d->act_dof[a] >= d->nv)
+      return "actuator address outside qpos / qvel";
+  return nullptr;
+}
 }  // namespace
 
 extern "C" {
@@ -103,6 +247,44 @@ int duck_episode_accumulate(int n, int nmetrics, const float* reward, const floa
     return duck_fail(DUCK_EINVAL, "duck_episode_accumulate: null pointer");
   hipLaunchKernelGGL(episode_accumulate_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, nmetrics,
                      reward, done, metrics, metrics_stride, mode, run, fin, flag);
+  HIPCHECK(hipGetLastError());
+  return DUCK_OK;
+}
+
+int duck_fleet_observe(const duck_fleet_desc* d, int n, const float* qpos, const float* qvel, const float* aux,
+                       float* ctl, float* obs, float* acc, float* alive, void* stream) {
+  g_err.clear();
+  if (!d || !qpos || !qvel || !aux || !ctl || !obs || !acc || !alive)
+    return duck_fail(DUCK_EINVAL, "duck_fleet_observe: null pointer");
+  if (n < 0 || n > (1 << 27)) return duck_fail(DUCK_EINVAL, "duck_fleet_observe: bad size (0 <= N <= 2^27)");
+  if (const char* why = fleet_desc_error(d)) return duck_fail(DUCK_EINVAL, std::string("duck_fleet_observe: ") + why);
+  // every aux row the kernel reads lies inside the record
+  const int sensors[4] = {d->gyro, d->accelerometer, d->upvector, d->local_linvel};
+  for (int s : sensors)
+    if (s < 0 || d->sens_off < 0 || (long long)d->sens_off + s + 3 > d->naux)
+      return duck_fail(DUCK_EINVAL, "duck_fleet_observe: sensor address outside the aux record");
+  for (int f : d->foot_con)
+    if (f < 0 || d->con_off < 0 || (long long)d->con_off + f + 4 > d->naux)
+      return duck_fail(DUCK_EINVAL, "duck_fleet_observe: contact slot outside the aux record");
+  if (!d->standing && d->nb_steps_in_period < 1)
+    return duck_fail(DUCK_EINVAL, "duck_fleet_observe: nb_steps_in_period must be >= 1 unless standing");
+  if (n == 0) return DUCK_OK;
+  const int per = FLEET_TPB / FLEET_TEAM;
+  hipLaunchKernelGGL(fleet_observe_kernel, dim3((n + per - 1) / per), dim3(FLEET_TPB), 0, (hipStream_t)stream, *d, n,
+                     qpos, qvel, aux, ctl, obs, acc, alive);
+  HIPCHECK(hipGetLastError());
+  return DUCK_OK;
+}
+
+int duck_fleet_actuate(const duck_fleet_desc* d, int n, const float* action, float* ctl, float* ctrl, void* stream) {
+  g_err.clear();
+  if (!d || !action || !ctl || !ctrl) return duck_fail(DUCK_EINVAL, "duck_fleet_actuate: null pointer");
+  if (n < 0 || n > (1 << 27)) return duck_fail(DUCK_EINVAL, "duck_fleet_actuate: bad size (0 <= N <= 2^27)");
+  if (const char* why = fleet_desc_error(d)) return duck_fail(DUCK_EINVAL, std::string("duck_fleet_actuate: ") + why);
+  if (n == 0) return DUCK_OK;
+  const int per = FLEET_TPB / FLEET_TEAM;
+  hipLaunchKernelGGL(fleet_actuate_kernel, dim3((n + per - 1) / per), dim3(FLEET_TPB), 0, (hipStream_t)stream, *d, n,
+                     action, ctl, ctrl);
   HIPCHECK(hipGetLastError());
   return DUCK_OK;
 }

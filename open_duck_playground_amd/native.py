@@ -27,7 +27,8 @@ EXPORTS = ["duck_version", "duck_build_id", "duck_last_error", "duck_layout_get"
            "duck_step_kernel_for", "duck_debug_lat_timeouts", "duck_gather_columns", "duck_mlp_group",
            "duck_device_error", "duck_gae_stats", "duck_ppo_loss_stats", "duck_mlp_group_bn", "duck_gather_columns_norm",
            "duck_column_stats", "duck_column_stats_scratch", "duck_clip_adam_reduce", "duck_ppo_loss_grad",
-           "duck_ppo_loss_sums", "duck_mlp_group_tiles", "duck_policy_act", "duck_episode_accumulate"]
+           "duck_ppo_loss_sums", "duck_mlp_group_tiles", "duck_policy_act", "duck_episode_accumulate",
+           "duck_fleet_observe", "duck_fleet_actuate"]
 
 
 class DuckMlpProblem(C.Structure):
@@ -41,6 +42,19 @@ class DuckMlpProblem(C.Structure):
 class DuckGatherField(C.Structure):
     """include/duck_ppo.h duck_gather_field"""
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("T", C.c_int), ("B", C.c_int), ("w", C.c_int)]
+
+
+FLEET_MAX_NU = 16
+
+
+class DuckFleetDesc(C.Structure):
+    """include/duck_fleet.h duck_fleet_desc"""
+    _fields_ = [("nq", C.c_int), ("nv", C.c_int), ("nu", C.c_int), ("naux", C.c_int), ("sens_off", C.c_int),
+                ("con_off", C.c_int), ("gyro", C.c_int), ("accelerometer", C.c_int), ("upvector", C.c_int),
+                ("local_linvel", C.c_int), ("act_qpos", C.c_int * FLEET_MAX_NU), ("act_dof", C.c_int * FLEET_MAX_NU),
+                ("act_default", C.c_float * FLEET_MAX_NU), ("foot_con", C.c_int * 2), ("dof_vel_scale", C.c_float),
+                ("action_scale", C.c_float), ("accel_x_offset", C.c_float), ("target_step", C.c_float),
+                ("nb_steps_in_period", C.c_int), ("standing", C.c_int), ("speed_limits", C.c_int)]
 
 
 class DuckError(RuntimeError):
@@ -314,6 +328,9 @@ def lib(path: str = None):
             L.duck_column_stats_scratch.argtypes = [C.c_int, C.c_int]
         if hasattr(L, "duck_episode_accumulate"):
             L.duck_episode_accumulate.argtypes = [C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
+        if hasattr(L, "duck_fleet_observe"):
+            L.duck_fleet_observe.argtypes = [C.POINTER(DuckFleetDesc), C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+            L.duck_fleet_actuate.argtypes = [C.POINTER(DuckFleetDesc), C.c_int, vp, vp, vp, vp]
         if hasattr(L, "duck_gather_columns"):
             L.duck_gather_columns.argtypes = [C.c_int, C.POINTER(DuckGatherField), vp, C.c_int, vp]
         if hasattr(L, "duck_mlp_gemm"):
