@@ -13,7 +13,10 @@
  *   duck_policy_act     self.policy.infer(obs) (mujoco_infer.py:203; duck_ppo.h)
  *   duck_fleet_actuate  the action history, motor targets, speed limit and ctrl (mujoco_infer.py:208-231)
  *
- * Both entries are model-agnostic: a host descriptor filled from the compiled model tells them where
+ * and, only when the caller disturbs the loop as the training env does (noise, changing commands, pushes),
+ * duck_fleet_disturb between duck_fleet_observe and duck_policy_act.
+ *
+ * The entries are model-agnostic: a host descriptor filled from the compiled model tells them where
  * the sensors, the actuated joints and the foot contacts are. Conventions are duck.h's: DEVICE
  * pointers, float32, no allocation, no synchronisation, work ordered on `stream`, negative codes with
  * duck_last_error(), DUCK_EINVAL on null pointers and bad sizes.
@@ -23,6 +26,8 @@
  */
 #ifndef DUCK_FLEET_H_
 #define DUCK_FLEET_H_
+
+#include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -94,6 +99,54 @@ int duck_fleet_observe(const duck_fleet_desc* desc, int N, const float* qpos, co
  * the next duck_physics_step's input) = motor_targets. */
 int duck_fleet_actuate(const duck_fleet_desc* desc, int N, const float* action, float* ctl, float* ctrl,
                        void* stream);
+
+/* Disturbances of the deployment loop: sensor noise on the observation the policy is about to see, the
+ * command of the next period from a schedule, and a push of the base before the next period's physics
+ * (the training env's, joystick.py:492-558, :449-477, :381-400). One more launch, between
+ * duck_fleet_observe and duck_policy_act; a loop that configures none of the three does not enqueue it.
+ *
+ * The period's count lives on the device: tick [N] int32, p = tick[e] the periods robot e completed before
+ * this one (0 at the loop's start, set by the caller), so that a captured graph, which freezes every host
+ * argument, replays the same launch for every period.
+ *
+ * Random stream, threefry2x32 (20 rounds): key = threefry2x32((seed low, seed high), (id low,
+ * DUCK_FLEET_KEY_TAG ^ id high)) with id = robot_offset + e, the robot's global id (csrc/duck_math.h
+ * derive_key); block b of period p is threefry2x32(key, (p, b)), whose two words are the slots 2b and 2b + 1;
+ * a slot's uniform is u = (word >> 9) * 2^-23 in [0, 1), exact in float32.
+ *   slot 0   u0, the push's magnitude        slot 1   u1, the push's direction
+ *   obs column k: slot 2 * (1 + k % 16 + 16 * (k / 32)) + (k / 16) % 2
+ * (columns k and k + 16 of an even k / 16 share a block: a lane of the 16-lane group evaluates it once).
+ * A robot's draws depend on (seed, id, p) only -- not on N, the launch geometry or graph replay.
+ *
+ * In this order, for robot e:
+ *   noise    for every obs column k < DUCK_FLEET_OBS_SIZE(nu) with noise_scale[k] != 0:
+ *            obs[e][k] = obs[e][k] + (2u - 1) * noise_scale[k]; 2u - 1 is exact, the product is rounded,
+ *            then the sum. A column of scale 0 is not written (a -0 keeps its bits). The bookkeeping of
+ *            duck_fleet_observe has run on the true sensors.
+ *   command  when sched != NULL, with t = p + 1: the 7 values of ctl.command =
+ *            sched[min(max(sched_id[e], 0), n_sched - 1)][min(t / seg_periods, n_seg - 1)] (the last
+ *            segment is held). sched [n_sched][n_seg][7] row-major float32, sched_id [N] int32.
+ *   push     when push != NULL: push [N][DUCK_FLEET_PUSH_SIZE] row-major =
+ *            {first, interval, mag_lo, mag_hi, theta_lo, theta_hi}, first and interval integer-valued,
+ *            0 <= . < 2^24. A push is due at t = p + 1 (it acts before period t's physics) when first >= 1 and
+ *            (t == first, or interval > 0 and t > first and (t - first) % interval == 0); first == 0 never
+ *            pushes. When due: mag = mag_lo + (mag_hi - mag_lo) * u0, theta = theta_lo + (theta_hi - theta_lo)
+ *            * u1 (lo == hi gives lo), qvel[0][e] += cosf(theta) * mag, qvel[1][e] += sinf(theta) * mag with
+ *            the accurate functions, every product and sum rounded on its own. No other qvel row is written
+ *            (desc.nv >= 2 is required with a push table).
+ *   tick     tick[e] = p + 1.
+ * desc gives nu (the widths of ctl and obs) and nv. N == 0 launches nothing. */
+#define DUCK_FLEET_PUSH_SIZE 6
+#define DUCK_FLEET_KEY_TAG 0xF1EEu
+typedef struct {
+  uint64_t seed;
+  int n_sched, n_seg, seg_periods; /* the schedule table's shape; each >= 1 when sched != NULL, else unused */
+  float noise_scale[DUCK_FLEET_OBS_SIZE(DUCK_FLEET_MAX_NU)]; /* per obs column, the level folded in; 0: untouched */
+} duck_fleet_disturbance;
+
+int duck_fleet_disturb(const duck_fleet_desc* desc, const duck_fleet_disturbance* dis, int N, int64_t robot_offset,
+                       int32_t* tick, const float* sched, const int32_t* sched_id, const float* push, float* qvel,
+                       float* ctl, float* obs, void* stream);
 
 #ifdef __cplusplus
 }

@@ -3,6 +3,7 @@
 // variant (variant_*.hip). Every entry returns DUCK_OK or a negative code with a
 // thread-local message; no entry allocates, synchronises or throws on the step path.
 #include "duck_common.h"
+#include "duck_math.h"
 #include "../../include/duck_fleet.h"
 #include "../../include/duck_ppo.h"
 
@@ -225,6 +226,77 @@ __global__ __launch_bounds__(FLEET_TPB) void fleet_actuate_kernel(const duck_fle
   ctrl[(size_t)a * n + e] = mt;
 }
 
+// The loop's disturbances (include/duck_fleet.h: duck_fleet_disturb), the same 16-lane group per robot. Lane l
+// takes the noise of the obs columns l, l + 16, ...: columns l + 32 j and l + 32 j + 16 are the two words of
+// threefry block 1 + l + 16 j, evaluated once and only when one of the two has a scale. Lanes 0-6 copy the
+// next period's command, lane 0 pushes the base and advances the tick. Every lane has read the tick (one
+// load of the whole wave) before lane 0's store, which depends on it, can issue. No LDS, no votes: lanes
+// past the last robot leave.
+__device__ __forceinline__ float fleet_u23(uint32_t w) { return (float)(w >> 9) * (1.0f / 8388608.0f); }
+
+__global__ __launch_bounds__(FLEET_TPB) void fleet_disturb_kernel(const duck_fleet_disturbance S, int nu, int noisy,
+                                                                  int n, long long robot_offset, int* tick,
+                                                                  const float* __restrict__ sched,
+                                                                  const int* __restrict__ sched_id,
+                                                                  const float* __restrict__ push,
+                                                                  float* __restrict__ qvel, float* __restrict__ ctl,
+                                                                  float* __restrict__ obs) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x % FLEET_TEAM;
+  const int e0 = blockIdx.x * (FLEET_TPB / FLEET_TEAM) + threadIdx.x / FLEET_TEAM;
+  if (e0 >= n) return;
+  const size_t e = e0, N = n;
+  const int C = DUCK_FLEET_CTL_SIZE(nu), O = DUCK_FLEET_OBS_SIZE(nu);
+  const int p = tick[e], t = p + 1;
+  Rng r;
+  derive_key(S.seed, robot_offset + (long long)e, DUCK_FLEET_KEY_TAG, r.k0, r.k1);
+  r.ctr = (uint32_t)p;
+
+  if (noisy) {
+    float* o = obs + e * O;
+    for (int k = lane; k < O; k += 2 * FLEET_TEAM) {
+      const int k1 = k + FLEET_TEAM;
+      const float s0 = S.noise_scale[k], s1 = k1 < O ? S.noise_scale[k1] : 0.f;
+      if (s0 != 0.f || s1 != 0.f) {
+        uint32_t a, b;
+        threefry2x32(r.k0, r.k1, r.ctr, 1u + (uint32_t)lane + (uint32_t)(k / (2 * FLEET_TEAM)) * FLEET_TEAM, a, b);
+        if (s0 != 0.f) {
+          const float d = (2.f * fleet_u23(a) - 1.f) * s0;
+          o[k] = o[k] + d;
+        }
+        if (s1 != 0.f) {
+          const float d = (2.f * fleet_u23(b) - 1.f) * s1;
+          o[k1] = o[k1] + d;
+        }
+      }
+    }
+  }
+
+  if (sched && lane < 7) {
+    int id = sched_id[e], seg = t / S.seg_periods;
+    id = id < 0 ? 0 : (id > S.n_sched - 1 ? S.n_sched - 1 : id);
+    seg = seg < 0 ? 0 : (seg > S.n_seg - 1 ? S.n_seg - 1 : seg);  // (a negative tick reads segment 0, not before the table)
+    ctl[e * C + 5 * nu + lane] = sched[((size_t)id * S.n_seg + seg) * 7 + lane];
+  }
+
+  if (lane == 0) {
+    if (push) {  // joystick.py:381-400
+      const float* w = push + e * DUCK_FLEET_PUSH_SIZE;
+      const int first = (int)w[0], interval = (int)w[1];
+      if (first >= 1 && (t == first || (interval > 0 && t > first && (t - first) % interval == 0))) {
+        uint32_t a, b;
+        threefry2x32(r.k0, r.k1, r.ctr, 0u, a, b);
+        const float dm = (w[3] - w[2]) * fleet_u23(a), dt = (w[5] - w[4]) * fleet_u23(b);
+        const float mag = w[2] + dm, theta = w[4] + dt;
+        const float dx = cosf(theta) * mag, dy = sinf(theta) * mag;
+        qvel[e] = qvel[e] + dx;
+        qvel[N + e] = qvel[N + e] + dy;
+      }
+    }
+    tick[e] = t;
+  }
+}
+
 static const char* fleet_desc_error(const duck_fleet_desc* d) {
   if (d->nq < 1 || d->nv < 1 || d->nu < 1 || d->nu > DUCK_FLEET_MAX_NU) return "nq, nv >= 1 and 1 <= nu <= 16";
   for (int a = 0; a < d->nu; a++)
@@ -285,6 +357,27 @@ int duck_fleet_actuate(const duck_fleet_desc* d, int n, const float* action, flo
   const int per = FLEET_TPB / FLEET_TEAM;
   hipLaunchKernelGGL(fleet_actuate_kernel, dim3((n + per - 1) / per), dim3(FLEET_TPB), 0, (hipStream_t)stream, *d, n,
                      action, ctl, ctrl);
+  HIPCHECK(hipGetLastError());
+  return DUCK_OK;
+}
+
+int duck_fleet_disturb(const duck_fleet_desc* d, const duck_fleet_disturbance* dis, int n, int64_t robot_offset,
+                       int32_t* tick, const float* sched, const int32_t* sched_id, const float* push, float* qvel,
+                       float* ctl, float* obs, void* stream) {
+  g_err.clear();
+  if (!d || !dis || !tick || !qvel || !ctl || !obs) return duck_fail(DUCK_EINVAL, "duck_fleet_disturb: null pointer");
+  if (sched && !sched_id) return duck_fail(DUCK_EINVAL, "duck_fleet_disturb: a schedule needs sched_id");
+  if (sched && (dis->n_sched < 1 || dis->n_seg < 1 || dis->seg_periods < 1))
+    return duck_fail(DUCK_EINVAL, "duck_fleet_disturb: a schedule needs n_sched, n_seg, seg_periods >= 1");
+  if (n < 0 || n > (1 << 27)) return duck_fail(DUCK_EINVAL, "duck_fleet_disturb: bad size (0 <= N <= 2^27)");
+  if (const char* why = fleet_desc_error(d)) return duck_fail(DUCK_EINVAL, std::string("duck_fleet_disturb: ") + why);
+  if (push && d->nv < 2) return duck_fail(DUCK_EINVAL, "duck_fleet_disturb: a push table needs nv >= 2");
+  if (n == 0) return DUCK_OK;
+  int noisy = 0;
+  for (int k = 0; k < DUCK_FLEET_OBS_SIZE(d->nu); k++) noisy |= dis->noise_scale[k] != 0.f;
+  const int per = FLEET_TPB / FLEET_TEAM;
+  hipLaunchKernelGGL(fleet_disturb_kernel, dim3((n + per - 1) / per), dim3(FLEET_TPB), 0, (hipStream_t)stream, *dis,
+                     d->nu, noisy, n, (long long)robot_offset, tick, sched, sched_id, push, qvel, ctl, obs);
   HIPCHECK(hipGetLastError());
   return DUCK_OK;
 }

@@ -28,7 +28,7 @@ EXPORTS = ["duck_version", "duck_build_id", "duck_last_error", "duck_layout_get"
            "duck_device_error", "duck_gae_stats", "duck_ppo_loss_stats", "duck_mlp_group_bn", "duck_gather_columns_norm",
            "duck_column_stats", "duck_column_stats_scratch", "duck_clip_adam_reduce", "duck_ppo_loss_grad",
            "duck_ppo_loss_sums", "duck_mlp_group_tiles", "duck_policy_act", "duck_episode_accumulate",
-           "duck_fleet_observe", "duck_fleet_actuate"]
+           "duck_fleet_observe", "duck_fleet_actuate", "duck_fleet_disturb"]
 
 
 class DuckMlpProblem(C.Structure):
@@ -55,6 +55,15 @@ class DuckFleetDesc(C.Structure):
                 ("act_default", C.c_float * FLEET_MAX_NU), ("foot_con", C.c_int * 2), ("dof_vel_scale", C.c_float),
                 ("action_scale", C.c_float), ("accel_x_offset", C.c_float), ("target_step", C.c_float),
                 ("nb_steps_in_period", C.c_int), ("standing", C.c_int), ("speed_limits", C.c_int)]
+
+
+FLEET_PUSH_SIZE = 6
+
+
+class DuckFleetDisturbance(C.Structure):
+    """include/duck_fleet.h duck_fleet_disturbance"""
+    _fields_ = [("seed", C.c_uint64), ("n_sched", C.c_int), ("n_seg", C.c_int), ("seg_periods", C.c_int),
+                ("noise_scale", C.c_float * (17 + 6 * FLEET_MAX_NU))]
 
 
 class DuckError(RuntimeError):
@@ -331,6 +340,8 @@ def lib(path: str = None):
         if hasattr(L, "duck_fleet_observe"):
             L.duck_fleet_observe.argtypes = [C.POINTER(DuckFleetDesc), C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
             L.duck_fleet_actuate.argtypes = [C.POINTER(DuckFleetDesc), C.c_int, vp, vp, vp, vp]
+            L.duck_fleet_disturb.argtypes = [C.POINTER(DuckFleetDesc), C.POINTER(DuckFleetDisturbance), C.c_int,
+                                             C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp]
         if hasattr(L, "duck_gather_columns"):
             L.duck_gather_columns.argtypes = [C.c_int, C.POINTER(DuckGatherField), vp, C.c_int, vp]
         if hasattr(L, "duck_mlp_gemm"):

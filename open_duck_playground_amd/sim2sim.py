@@ -16,7 +16,9 @@ phase (cos, sin) advanced by ``phase_frequency_factor`` per period (:184-205).
 ``FleetInfer`` is the same loop for N robots, resident on the device (include/duck_fleet.h): the question a
 user has of an exported policy -- does it track commands over the whole command box, does it survive the
 randomised models -- takes thousands of runs. ``python -m open_duck_playground_amd.sim2sim`` keeps the
-reference's flags and adds ``--num_robots``, ``--periods``, ``--command_grid``, ``--randomize``, ``--out``.
+reference's flags and adds ``--num_robots``, ``--periods``, ``--command_grid``, ``--randomize``, ``--out``, and the
+disturbances the training env has and the reference's deployment loop lacks: ``--push_grid``, ``--push_at``,
+``--push_every``, ``--recovery_window``, ``--noise``, ``--noise_seed``, ``--resample_commands``.
 """
 
 from __future__ import annotations
@@ -224,13 +226,21 @@ class FleetInfer:
     tracking errors until the robot falls (``report()``); fallen robots keep being simulated and controlled.
 
     The first ``run`` is eager; later ones replay a captured graph of ``CHUNK`` periods (one stream, a
-    linear graph) and run the remainder eagerly."""
+    linear graph) and run the remainder eagerly.
 
-    CHUNK = 50   # control periods per captured graph (200 launches)
+    Disturbances (all off by default; ``set_command_schedule``, ``set_pushes``, ``set_noise`` or the
+    keyword arguments of the same names, each the tuple of its setter's arguments): when any is
+    configured, a period is physics -> observe -> duck_fleet_disturb -> policy -> actuate, the fifth launch
+    adding sensor noise to the observation, writing the next period's command and pushing the base before
+    the next period's physics. The period count ``tick`` lives on the device, so a captured graph replays it.
+    With none configured the loop is the four launches above, unchanged."""
+
+    CHUNK = 50   # control periods per captured graph (200 launches, 250 with disturbances)
 
     def __init__(self, model_path: str = "flat_terrain", onnx_model_path: Optional[str] = None, num_robots: int = 1,
                  reference_data: Optional[str] = None, standing: bool = False, device="cuda:0",
-                 randomize: Optional[int] = None):
+                 randomize: Optional[int] = None, command_schedule: Optional[tuple] = None,
+                 pushes: Optional[tuple] = None, noise: Optional[tuple] = None):
         import ctypes as C
 
         from .native import DuckError, check
@@ -287,12 +297,24 @@ class FleetInfer:
                                            self._stream()), self._lib)
         self.default_actuator = np.asarray(m.key_ctrl[m.names["key"].index("home")], dtype=np.float32)
         self.calls, self.graph = 0, None
+        # the disturbances (include/duck_fleet.h duck_fleet_disturb): all off
+        from .native import DuckFleetDisturbance
+        self.tick = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.dis = DuckFleetDisturbance()
+        self.sched = self.sched_id = self.push = None
         self.restart()
+        if command_schedule is not None:
+            self.set_command_schedule(*command_schedule)
+        if pushes is not None:
+            self.set_pushes(*pushes)
+        if noise is not None:
+            self.set_noise(*noise)
 
     def restart(self) -> None:
         """Every robot back to the loop's start, with the randomisation record ``dr`` as it is now.
         MJInferBase.__init__: MjData at qpos0 with zero ctrl, one mj_step, then the home keyframe's qpos and
-        ctrl (the velocity of that first step is kept); mujoco_infer.py:49-60 for the control record."""
+        ctrl (the velocity of that first step is kept); mujoco_infer.py:49-60 for the control record. The
+        period count goes back to 0 and a command schedule to its segment 0."""
         m, n = self.model, self.num_robots
         col = lambda a: torch.tensor(np.asarray(a, dtype=np.float32)[:, None], device=self.device)  # noqa: E731
         key = m.names["key"].index("home")
@@ -306,6 +328,8 @@ class FleetInfer:
         self.ctl_field("motor_targets").copy_(default.expand(n, -1))
         self.ctl_field("prev_motor_targets").copy_(default.expand(n, -1))
         self.ctl_field("phase_frequency_factor").fill_(1.0)
+        self.tick.zero_()
+        self._schedule_command()   # segment 0 of a schedule, if one is set
         self.reset_report()
 
     # --- launches -----------------------------------------------------------------------------
@@ -339,10 +363,26 @@ class FleetInfer:
         self._check(L.duck_fleet_actuate(C.byref(self.desc), self.num_robots, self.action.data_ptr(),
                                          self.ctl.data_ptr(), self.ctrl.data_ptr(), self._stream()), L)
 
+    def disturbed(self) -> bool:
+        """Whether a schedule, a push table or a non-zero noise is set (the loop's fifth launch)."""
+        return self.sched is not None or self.push is not None or any(self.dis.noise_scale)
+
+    def disturb(self):
+        """duck_fleet_disturb on this period's ``obs``: noise, the next period's command and push, the tick."""
+        import ctypes as C
+        L = self._lib
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        self._check(L.duck_fleet_disturb(C.byref(self.desc), C.byref(self.dis), self.num_robots, 0, self.tick.data_ptr(),
+                                         ptr(self.sched), ptr(self.sched_id), ptr(self.push), self.qvel.data_ptr(),
+                                         self.ctl.data_ptr(), self.obs.data_ptr(), self._stream()), L)
+
     def _periods(self, k: int, rec: Optional[torch.Tensor] = None, t0: int = 0):
+        disturbed = self.disturbed()
         for t in range(k):
             self._physics(self.decimation)
             self.observe()
+            if disturbed:
+                self.disturb()
             if rec is not None:
                 rec[t0 + t].copy_(self.obs)
             self.act()
@@ -385,6 +425,118 @@ class FleetInfer:
         if c.shape not in ((7,), (self.num_robots, 7)):
             raise DuckError(f"commands must be [7] or [{self.num_robots}][7], got {tuple(c.shape)}")
         self.ctl_field("command").copy_(c.expand(self.num_robots, 7))
+
+    # --- disturbances (include/duck_fleet.h duck_fleet_disturb) -------------------------------------
+    def _schedule_command(self) -> None:
+        """``ctl.command`` = the schedule's segment of the current tick (segment 0 after ``restart``)."""
+        if self.sched is None:
+            return
+        seg = torch.clamp(self.tick.long() // int(self.dis.seg_periods), max=int(self.dis.n_seg) - 1)
+        self.ctl_field("command").copy_(self.sched[self.sched_id.long(), seg])
+
+    def set_command_schedule(self, table, ids=None, seg_periods: int = 1) -> None:
+        """Commands that change while the robots walk (the reference loop is driven from a keyboard,
+        mujoco_infer.py:105-154; the training env resamples every 500 steps, joystick.py:449-477).
+        ``table`` [S][K][7]: S schedules of K segments; robot r follows schedule ``ids[r]`` ([N], default
+        r mod S), one segment per ``seg_periods`` control periods, the last one held. The command of the
+        period now due is written at once. ``table=None`` turns the schedule off (the commands stay)."""
+        from .native import DuckError
+        n = self.num_robots
+        if table is None:
+            if self.sched is not None:
+                self.sched = self.sched_id = None
+                self.graph = None
+            return
+        tab = np.asarray(table, dtype=np.float32)
+        if tab.ndim != 3 or tab.shape[0] < 1 or tab.shape[1] < 1 or tab.shape[2] != 7:
+            raise DuckError(f"a command schedule is [S][K][7] with S, K >= 1, got {tuple(tab.shape)}")
+        if not np.isfinite(tab).all():
+            raise DuckError("a command schedule must be finite")
+        idv = np.arange(n) % tab.shape[0] if ids is None else np.asarray(ids)
+        if idv.shape != (n,) or not np.issubdtype(idv.dtype, np.integer):
+            raise DuckError(f"schedule ids must be [{n}] integers, got {idv.dtype} {tuple(idv.shape)}")
+        if idv.min() < 0 or idv.max() >= tab.shape[0]:
+            raise DuckError(f"schedule ids must lie in [0, {tab.shape[0]}), got [{idv.min()}, {idv.max()}]")
+        if int(seg_periods) != seg_periods or int(seg_periods) < 1 or int(seg_periods) >= 2 ** 31:
+            raise DuckError(f"seg_periods must be an integer >= 1, got {seg_periods!r}")
+        shape = (int(self.dis.n_sched), int(self.dis.n_seg), int(self.dis.seg_periods))
+        new = tab.shape[:2] + (int(seg_periods),)
+        if self.sched is None or shape != new:     # new buffers, or a value the captured launch took by value
+            self.sched = torch.empty(tab.shape, dtype=torch.float32, device=self.device)
+            self.sched_id = torch.empty(n, dtype=torch.int32, device=self.device)
+            self.dis.n_sched, self.dis.n_seg, self.dis.seg_periods = new
+            self.graph = None
+        self.sched.copy_(torch.as_tensor(tab))
+        self.sched_id.copy_(torch.as_tensor(idv.astype(np.int32)))
+        self._schedule_command()
+
+    def set_pushes(self, first=None, interval=0, magnitude=0.0, theta=0.0) -> None:
+        """Pushes of the base (joystick.py:381-400): at the start of period ``first`` (>= 1; 0: never) and,
+        with ``interval`` > 0, every ``interval`` periods after it, the base's linear velocity gains
+        magnitude * (cos theta, sin theta) in the world frame, just before that period's physics.
+        ``first`` and ``interval`` are a scalar or [N] of integers; ``magnitude`` (m/s) and ``theta`` (rad)
+        are a scalar, an [N] list or array, or a tuple ``(lo, hi)`` of such, drawn uniformly per push from
+        the disturbance stream (``set_noise``'s seed). ``first=None`` turns pushes off."""
+        from .native import FLEET_PUSH_SIZE, DuckError
+        n = self.num_robots
+        if first is None:
+            if self.push is not None:
+                self.push = None
+                self.graph = None
+            return
+        if self.model.nv < 2:
+            raise DuckError("a push needs a base with at least two velocity rows")
+        row = np.zeros((n, FLEET_PUSH_SIZE), dtype=np.float32)
+
+        def column(name, v):
+            a = np.asarray(v, dtype=np.float64)
+            if a.shape not in ((), (n,)):
+                raise DuckError(f"{name} must be a scalar or [{n}], got {tuple(a.shape)}")
+            if not np.isfinite(a).all():
+                raise DuckError(f"{name} must be finite")
+            return np.broadcast_to(a, (n,))
+        for k, (name, v) in enumerate((("first", first), ("interval", interval))):
+            a = column(name, v)
+            if (a != np.floor(a)).any() or (a < 0).any() or (a >= 2 ** 24).any():
+                raise DuckError(f"{name} must be integers in [0, 2^24)")
+            row[:, k] = a
+        for k, (name, v) in enumerate((("magnitude", magnitude), ("theta", theta))):
+            lo, hi = v if isinstance(v, tuple) else (v, v)
+            if isinstance(v, tuple) and len(v) != 2:
+                raise DuckError(f"{name} as a tuple is (lo, hi), got {len(v)} values")
+            row[:, 2 + 2 * k], row[:, 3 + 2 * k] = column(name, lo), column(name, hi)
+        if self.push is None:
+            self.push = torch.empty(n, FLEET_PUSH_SIZE, dtype=torch.float32, device=self.device)
+            self.graph = None
+        self.push.copy_(torch.as_tensor(row))
+
+    def default_noise_scales(self) -> np.ndarray:
+        """The training env's noise scales per obs column (config.default_config().noise_config, joystick.py:
+        492-558): gyro, accelerometer, the bug-compatible config.qpos_noise_scale on the joint angles and
+        joint_vel * dof_vel_scale on the joint velocities; every other column 0."""
+        return default_noise_scales(self.num_dofs, float(self.desc.dof_vel_scale))
+
+    def set_noise(self, level: float = 0.0, seed: int = 0, scales=None) -> None:
+        """Sensor noise on the observation the policy sees: column k gains U[-1, 1) * level * scales[k], drawn
+        per robot and period from the stream of ``seed`` (which also draws the random pushes). ``scales``
+        [obs_size] defaults to ``default_noise_scales()``. The training env adds the noise to the raw joint
+        velocity and scales by dof_vel_scale afterwards; here it is added to the scaled column, with the scale
+        multiplied in. duck_fleet_observe's bookkeeping has run on the true sensors; action and IMU delay
+        are not modelled. ``level=0`` turns the noise off."""
+        from .native import DuckError
+        sc = self.default_noise_scales() if scales is None else np.asarray(scales, dtype=np.float64)
+        if sc.shape != (self.obs_size,):
+            raise DuckError(f"noise scales must be [{self.obs_size}], got {tuple(sc.shape)}")
+        if not np.isfinite(level) or not np.isfinite(sc).all():
+            raise DuckError("the noise level and scales must be finite")
+        eff = (float(level) * sc).astype(np.float32)
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        old = np.array(self.dis.noise_scale[:self.obs_size], dtype=np.float32)
+        if seed != int(self.dis.seed) or old.tobytes() != eff.tobytes():   # taken by value by a captured launch
+            self.graph = None
+        self.dis.seed = seed
+        for k in range(self.obs_size):
+            self.dis.noise_scale[k] = float(eff[k])
 
     def state(self):
         """(qpos [N][nq], qvel [N][nv], ctrl [N][nu]) as numpy float32."""
@@ -449,6 +601,115 @@ def grid_report(rep: Dict[str, np.ndarray], acc: np.ndarray, cells: np.ndarray, 
     return out
 
 
+def default_noise_scales(nu: int, dof_vel_scale: float = 0.05) -> np.ndarray:
+    """float64 [17 + 6 nu]: the training env's noise scale of every obs column of the deployment loop
+    (``FleetInfer.default_noise_scales``)."""
+    from . import config
+    cfg = config.default_config()
+    sc = cfg.noise_config.scales
+    out = np.zeros(17 + 6 * nu)
+    out[0:3], out[3:6] = sc.gyro, sc.accelerometer
+    out[13:13 + nu] = config.qpos_noise_scale(cfg, max(nu, len(constants.JOINTS_ORDER_NO_HEAD)))[:nu]
+    out[13 + nu:13 + 2 * nu] = sc.joint_vel * dof_vel_scale
+    return out
+
+
+def push_grid(spec: str, magnitude_range=None) -> np.ndarray:
+    """``NMxND`` -> the [NM * ND][2] (magnitude, theta) push cells: NM magnitudes over
+    push_config.magnitude_range (both ends included; a single one is the middle) x ND directions over
+    [0, 2 pi), the end excluded."""
+    try:
+        nm, nd = (int(v) for v in spec.lower().split("x"))
+        assert min(nm, nd) >= 1
+    except Exception:
+        raise ValueError(f"--push_grid wants NMxND with positive integers, got {spec!r}") from None
+    if magnitude_range is None:
+        from . import config
+        magnitude_range = config.default_config().push_config.magnitude_range
+    lo, hi = (float(v) for v in magnitude_range)
+    mags = np.linspace(lo, hi, nm) if nm > 1 else np.array([0.5 * (lo + hi)])
+    return np.array([(m, 2.0 * np.pi * d / nd) for m in mags for d in range(nd)], dtype=np.float32)
+
+
+def robot_cells(num_robots: int, n_command: int, n_push: int = 1) -> Tuple[np.ndarray, np.ndarray]:
+    """Round-robin over command cell x push cell: robot r has command cell r mod n_command (as without
+    pushes) and push cell (r div n_command) mod n_push."""
+    r = np.arange(num_robots)
+    return r % n_command, (r // n_command) % n_push
+
+
+def resample_schedule(cells: np.ndarray, n_periods: int, every: int) -> np.ndarray:
+    """[S][K][7]: schedule s starts at command cell s and steps to the next cell (wrapping) every ``every``
+    periods, for as many segments as ``n_periods`` needs."""
+    k = max(1, -(-int(n_periods) // int(every)))
+    s = len(cells)
+    return np.stack([cells[(c + np.arange(k)) % s] for c in range(s)]).astype(np.float32)
+
+
+def push_report(rep: Dict[str, np.ndarray], push_cells: np.ndarray, first, interval, n_periods: int, window: int) -> list:
+    """Per push cell (``push_cells`` [N], each robot's cell): the count, the share that never fell, and the
+    share that fell within ``window`` periods after a push. A robot falls once: one that survived
+    ``rep["periods"]`` = P periods fell in period P, and a push at the start of period t (t = first, first +
+    interval, ... < n_periods; ``first``, ``interval`` scalars or [N]) is blamed when t <= P < t + window."""
+    cell = np.asarray(push_cells)
+    n = len(cell)
+    first = np.broadcast_to(np.asarray(first, dtype=np.int64), (n,))
+    interval = np.broadcast_to(np.asarray(interval, dtype=np.int64), (n,))
+    P, fell = np.asarray(rep["periods"]).astype(np.int64), np.asarray(rep["fell"], dtype=bool)
+    since = P - first                      # periods between the first push and the fall
+    last = np.where(interval > 0, since % np.maximum(interval, 1), since)   # ... and the latest push before it
+    pushed = (first >= 1) & (first < n_periods) & (since >= 0)
+    after = fell & pushed & (last < window)
+    out = []
+    for c in range(int(cell.max()) + 1 if n else 0):
+        m = cell == c
+        k = int(m.sum())
+        out.append({"cell": c, "count": k, "survival_rate": float(np.mean(~fell[m])) if k else None,
+                    "fell_after_push_rate": float(np.mean(after[m])) if k else None, "window": int(window)})
+    return out
+
+
+def add_disturbance_arguments(p) -> None:
+    p.add_argument("--push_grid", type=str, default=None, metavar="NMxND",
+                   help="NM push magnitudes over push_config.magnitude_range x ND directions over [0, 2 pi)")
+    p.add_argument("--push_at", type=int, default=100, metavar="PERIOD", help="the first push (>= 1)")
+    p.add_argument("--push_every", type=int, default=0, metavar="PERIODS", help="repeat the push (0 = once)")
+    p.add_argument("--recovery_window", type=int, default=100, metavar="PERIODS",
+                   help="a fall within this many periods after a push counts against the push")
+    p.add_argument("--noise", type=float, default=0.0, metavar="LEVEL",
+                   help="sensor noise at LEVEL x the training env's scales (1 = as trained)")
+    p.add_argument("--noise_seed", type=int, default=0, metavar="SEED")
+    p.add_argument("--resample_commands", type=int, default=0, metavar="PERIODS",
+                   help="step every robot through the command grid's cells every PERIODS periods")
+
+
+def disturbance_plan(args, cells: np.ndarray):
+    """The setters' arguments for the command line's disturbance flags, or None when none is given:
+    {"schedule": (table, ids, seg_periods) | None, "pushes": (first, interval, magnitude [N], theta [N]) | None,
+    "push_cells" [P][2], "push_cell" [N], "echo": the settings for the report}."""
+    if args.push_grid is None and not args.noise and not args.resample_commands:
+        return None
+    if args.resample_commands < 0 or args.push_every < 0 or args.recovery_window < 0:
+        raise ValueError("--resample_commands, --push_every and --recovery_window must be >= 0")
+    n = args.num_robots
+    plan = {"schedule": None, "pushes": None, "push_cells": None, "push_cell": None}
+    echo = {"push_grid": args.push_grid, "noise": args.noise, "noise_seed": args.noise_seed,
+            "resample_commands": args.resample_commands}
+    pcells = push_grid(args.push_grid) if args.push_grid is not None else np.zeros((1, 2), np.float32)
+    ccell, pcell = robot_cells(n, len(cells), len(pcells))
+    if args.push_grid is not None:
+        if args.push_at < 1:
+            raise ValueError("--push_at must be >= 1 (the first period cannot be pushed)")
+        plan["pushes"] = (args.push_at, args.push_every, pcells[pcell, 0], pcells[pcell, 1])
+        plan["push_cells"], plan["push_cell"] = pcells, pcell
+        echo.update(push_at=args.push_at, push_every=args.push_every, recovery_window=args.recovery_window)
+    if args.resample_commands:
+        plan["schedule"] = (resample_schedule(cells, args.periods, args.resample_commands), ccell.astype(np.int32),
+                            args.resample_commands)
+    plan["echo"] = echo
+    return plan
+
+
 def main(argv=None) -> int:
     import argparse
     import json
@@ -463,18 +724,35 @@ def main(argv=None) -> int:
     p.add_argument("--randomize", type=int, default=None, metavar="SEED")
     p.add_argument("--out", type=str, default=None, metavar="report.json")
     p.add_argument("--device", type=str, default="cuda:0")
+    add_disturbance_arguments(p)
     args = p.parse_args(argv)
     cells = command_grid(args.command_grid)
+    plan = disturbance_plan(args, cells)
     fleet = FleetInfer(args.model_path, args.onnx_model_path, args.num_robots, reference_data=args.reference_data,
                        standing=args.standing, device=args.device, randomize=args.randomize)
     fleet.set_commands(cells[np.arange(args.num_robots) % len(cells)])
+    if plan is not None:
+        if plan["schedule"] is not None:
+            fleet.set_command_schedule(*plan["schedule"])
+        if plan["pushes"] is not None:
+            fleet.set_pushes(*plan["pushes"])
+        if args.noise:
+            fleet.set_noise(args.noise, args.noise_seed)
     t0 = time.time()
     fleet.run(args.periods)
     dt = time.time() - t0
-    rows = grid_report(fleet.report(), fleet.acc.cpu().numpy(), cells, args.periods)
+    rep = fleet.report()
+    rows = grid_report(rep, fleet.acc.cpu().numpy(), cells, args.periods)
     doc = {"model_path": args.model_path, "onnx_model_path": args.onnx_model_path, "num_robots": args.num_robots,
            "periods": args.periods, "randomize": args.randomize, "standing": args.standing,
            "robot_periods_per_s": args.num_robots * args.periods / max(dt, 1e-9), "cells": rows}
+    if plan is not None:
+        doc["disturbance"] = plan["echo"]
+        if plan["pushes"] is not None:
+            doc["pushes"] = push_report(rep, plan["push_cell"], args.push_at, args.push_every, args.periods,
+                                        args.recovery_window)
+            for row in doc["pushes"]:
+                row["magnitude"], row["theta"] = (float(v) for v in plan["push_cells"][row["cell"]])
     text = json.dumps(doc, indent=1)
     if args.out:
         with open(args.out, "w") as f:
