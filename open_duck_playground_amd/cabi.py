@@ -1,4 +1,4 @@
-"""ctypes mirrors of the C-ABI structs in ``include/duck_model.h`` and ``include/duck_env.h``.
+"""The C-ABI structs and constants of ``include/*.h`` as ctypes, read from the headers (``cdecl.py``).
 
 Shared by the product binding (``native.py`` -> ``libduck.so``) and by the test-only
 oracle binding (``tests/oracle_ffi.py`` -> ``oracle/liboracle.so``). Nothing here computes
@@ -8,102 +8,32 @@ physics; it only lays out host memory for the C side.
 from __future__ import annotations
 
 import ctypes as C
+import os
 from dataclasses import dataclass
 from typing import Dict, List
 
 import numpy as np
 
+from . import cdecl
 from .mjcf import Model
 
 _I = C.POINTER(C.c_int)
 _D = C.POINTER(C.c_double)
 
-
-def _duck_h_int(name: str) -> int:
-    import os
-    import re
-    text = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "duck.h")).read()
-    return int(re.search(rf"^#define {name} (\d+)", text, re.M).group(1))
-
+INCLUDE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include")
+# The C ABI as include/*.h states it: every struct class, constant and prototype below and in native.py
+# is read from the headers. duck_mlp_problem's and duck_gather_field's pointers are device addresses,
+# which callers hold as integers.
+HEADERS = cdecl.Header(*(os.path.join(INCLUDE, f) for f in ("duck_model.h", "duck_env.h", "duck.h", "duck_ppo.h",
+                                                            "duck_fleet.h")),
+                       address_structs=("duck_mlp_problem", "duck_gather_field"))
 
 # words (uint64) of duck_debug_stage_cycles' buffer
-STAGE_CYCLES_WORDS = _duck_h_int("DUCK_STAGE_CYCLES_WORDS")
+STAGE_CYCLES_WORDS = HEADERS.consts["DUCK_STAGE_CYCLES_WORDS"]
 
-
-class DuckModelDesc(C.Structure):
-    _fields_ = [
-        ("nq", C.c_int), ("nv", C.c_int), ("nu", C.c_int), ("nbody", C.c_int), ("njnt", C.c_int),
-        ("ngeom", C.c_int), ("nsite", C.c_int), ("nsensor", C.c_int), ("nsensordata", C.c_int), ("npair", C.c_int),
-        ("timestep", C.c_double), ("gravity", C.c_double * 3), ("impratio", C.c_double), ("tolerance", C.c_double),
-        ("ls_tolerance", C.c_double), ("meaninertia", C.c_double),
-        ("iterations", C.c_int), ("ls_iterations", C.c_int), ("eulerdamp", C.c_int),
-        ("body_parentid", _I), ("body_rootid", _I), ("body_weldid", _I), ("body_jntnum", _I), ("body_jntadr", _I),
-        ("body_dofnum", _I), ("body_dofadr", _I),
-        ("body_pos", _D), ("body_quat", _D), ("body_ipos", _D), ("body_iquat", _D), ("body_mass", _D),
-        ("body_inertia", _D), ("body_invweight0", _D),
-        ("jnt_type", _I), ("jnt_qposadr", _I), ("jnt_dofadr", _I), ("jnt_bodyid", _I), ("jnt_limited", _I),
-        ("jnt_pos", _D), ("jnt_axis", _D), ("jnt_range", _D), ("jnt_margin", _D), ("jnt_solref", _D),
-        ("jnt_solimp", _D),
-        ("dof_bodyid", _I), ("dof_jntid", _I), ("dof_parentid", _I),
-        ("dof_armature", _D), ("dof_damping", _D), ("dof_frictionloss", _D), ("dof_invweight0", _D),
-        ("dof_solref", _D), ("dof_solimp", _D),
-        ("geom_type", _I), ("geom_bodyid", _I), ("geom_dataid", _I),
-        ("geom_pos", _D), ("geom_quat", _D), ("geom_rbound", _D), ("geom_size", _D),
-        ("pair_geom1", _I), ("pair_geom2", _I), ("pair_condim", _I),
-        ("pair_friction", _D), ("pair_solref", _D), ("pair_solimp", _D), ("pair_margin", _D),
-        ("hull_nvert", C.c_int), ("hull_nface", C.c_int), ("hull_nedge", C.c_int),
-        ("hull_vert", _D), ("hull_face_normal", _D), ("hull_face_offset", _D), ("hull_edge", _I),
-        ("hfield_nrow", C.c_int), ("hfield_ncol", C.c_int), ("hfield_size", C.c_double * 4), ("hfield_data", _D),
-        ("site_bodyid", _I), ("site_pos", _D), ("site_quat", _D),
-        ("actuator_trnid", _I), ("actuator_ctrllimited", _I), ("actuator_forcelimited", _I),
-        ("actuator_kp", _D), ("actuator_kv", _D), ("actuator_gear", _D), ("actuator_ctrlrange", _D),
-        ("actuator_forcerange", _D),
-        ("sensor_type", _I), ("sensor_objid", _I), ("sensor_adr", _I), ("sensor_dim", _I),
-        ("qpos0", _D),
-    ]
-
-
-class DuckEnvConfig(C.Structure):
-    _fields_ = [
-        ("ctrl_dt", C.c_float), ("sim_dt", C.c_float), ("n_substeps", C.c_int),
-        ("episode_length", C.c_int), ("auto_reset", C.c_int),
-        ("action_scale", C.c_float), ("dof_vel_scale", C.c_float), ("max_motor_velocity", C.c_float),
-        ("use_imitation", C.c_int), ("use_motor_speed_limits", C.c_int),
-        ("noise_level", C.c_float),
-        ("action_min_delay", C.c_int), ("action_max_delay", C.c_int), ("imu_min_delay", C.c_int),
-        ("imu_max_delay", C.c_int),
-        ("noise_gyro", C.c_float), ("noise_accelerometer", C.c_float), ("noise_gravity", C.c_float),
-        ("noise_joint_vel", C.c_float),
-        ("qpos_noise_scale", C.c_float * 16),
-        ("scale_tracking_lin_vel", C.c_float), ("scale_tracking_ang_vel", C.c_float), ("scale_torques", C.c_float),
-        ("scale_action_rate", C.c_float), ("scale_alive", C.c_float), ("scale_imitation", C.c_float),
-        ("scale_stand_still", C.c_float),
-        ("tracking_sigma", C.c_float),
-        ("push_enable", C.c_int),
-        ("push_interval_range", C.c_float * 2), ("push_magnitude_range", C.c_float * 2),
-        ("lin_vel_x", C.c_float * 2), ("lin_vel_y", C.c_float * 2), ("ang_vel_yaw", C.c_float * 2),
-        ("neck_pitch_range", C.c_float * 2), ("head_pitch_range", C.c_float * 2), ("head_yaw_range", C.c_float * 2),
-        ("head_roll_range", C.c_float * 2), ("head_range_factor", C.c_float),
-        ("default_actuator", C.c_float * 16), ("init_qpos", C.c_float * 40),
-        ("actuator_qposadr", C.c_int * 16), ("actuator_qveladr", C.c_int * 16), ("backlash_qposadr", C.c_int * 16),
-        ("imu_site", C.c_int), ("left_foot_site", C.c_int), ("right_foot_site", C.c_int),
-        ("floor_geom", C.c_int), ("left_foot_geom", C.c_int), ("right_foot_geom", C.c_int),
-        ("sens_gyro", C.c_int), ("sens_accelerometer", C.c_int), ("sens_upvector", C.c_int),
-        ("sens_local_linvel", C.c_int), ("sens_global_angvel", C.c_int), ("sens_left_foot_linvel", C.c_int),
-        ("sens_right_foot_linvel", C.c_int),
-        ("domain_randomize", C.c_int),
-        ("task", C.c_int), ("scale_orientation", C.c_float), ("scale_head_pos", C.c_float),
-    ]
-
-
-class DuckRefMotion(C.Structure):
-    _fields_ = [
-        ("n_dx", C.c_int), ("n_dy", C.c_int), ("n_dtheta", C.c_int), ("n_dim", C.c_int), ("n_coef", C.c_int),
-        ("nb_steps_in_period", C.c_int),
-        ("dxs", C.c_float * 16), ("dys", C.c_float * 16), ("dthetas", C.c_float * 16),
-        ("dx_range", C.c_float * 2), ("dy_range", C.c_float * 2), ("dtheta_range", C.c_float * 2),
-        ("frames", C.POINTER(C.c_float)), ("coeffs", C.POINTER(C.c_double)),
-    ]
+DuckModelDesc = HEADERS.structs["duck_model_desc"]
+DuckEnvConfig = HEADERS.structs["duck_env_config"]
+DuckRefMotion = HEADERS.structs["duck_refmotion"]
 
 
 class ModelDescHolder:

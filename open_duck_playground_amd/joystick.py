@@ -33,7 +33,7 @@ import torch
 
 from . import config as cfgmod
 from . import constants
-from .cabi import METRIC_NAMES, TASK_JOYSTICK, ModelDescHolder, dr_layout, layout, refmotion_struct
+from .cabi import HEADERS, METRIC_NAMES, TASK_JOYSTICK, ModelDescHolder, dr_layout, layout, refmotion_struct
 from .config import ConfigDict, default_config  # noqa: F401  (re-exported like the reference module)
 from .mjcf import JNT_FREE, Model
 from .native import DuckError, check, lib, model_library
@@ -41,8 +41,8 @@ from .refmotion import PolyReferenceMotion
 
 USE_IMITATION_REWARD = cfgmod.USE_IMITATION_REWARD
 USE_MOTOR_SPEED_LIMITS = cfgmod.USE_MOTOR_SPEED_LIMITS
-# duck_set_step_mode (include/duck.h DUCK_STEP_*)
-STEP_MODES = {"auto": 0, "throughput": 1, "latency": 2, "paired": 3, "latency_x2": 4}
+# duck_set_step_mode (include/duck.h DUCK_STEP_*): "auto", "throughput", "latency", "paired", "latency_x2"
+STEP_MODES = {k[len("DUCK_STEP_"):].lower(): v for k, v in HEADERS.consts.items() if k.startswith("DUCK_STEP_")}
 
 
 @dataclass
@@ -214,8 +214,7 @@ class Joystick(OpenDuckMiniV2Env):
                                     dev, C.byref(handle)), self._lib)
         self._sim = handle
         self._scratch = None
-        if hasattr(self._lib, "duck_set_step_mode"):  # (A/B baselines built before the latency kernel)
-            check(self._lib.duck_set_step_mode(self._sim, STEP_MODES[self._step_mode]), self._lib)
+        check(self._lib.duck_set_step_mode(self._sim, STEP_MODES[self._step_mode]), self._lib)
 
     def set_step_mode(self, mode: str) -> None:
         """duck_set_step_mode: "auto" (default), "throughput", "latency", "paired" or "latency_x2". The same stage code
@@ -227,19 +226,15 @@ class Joystick(OpenDuckMiniV2Env):
         kernel at two workgroups per CU. Every mode gives bit-identical results (include/duck.h)."""
         if mode not in STEP_MODES:
             raise DuckError(f"step mode {mode!r} not in {sorted(STEP_MODES)}")
-        if not hasattr(self._lib, "duck_set_step_mode") and mode in ("auto", "throughput"):
-            return  # an A/B baseline library without the latency kernel
         self._step_mode = mode
         check(self._lib.duck_set_step_mode(self._sim, STEP_MODES[mode]), self._lib)
 
     @property
     def step_kernel(self) -> str:
         """The kernel step() launches for this batch: "throughput", "latency", "paired" or "latency_x2"."""
-        if not hasattr(self._lib, "duck_step_kernel_for"):
-            return "throughput"
         k = self._lib.duck_step_kernel_for(self._sim, self.num_envs)
         check(min(k, 0), self._lib)
-        return {1: "throughput", 2: "latency", 3: "paired", 4: "latency_x2"}[k]
+        return {v: name for name, v in STEP_MODES.items()}[k]
 
     def device_error(self, clear: bool = False) -> int:
         """The handle's sticky device error word (duck_device_error; DUCK_DEVERR_* bits, 0 = none). While

@@ -10,7 +10,7 @@ import ctypes as C
 import os
 import subprocess
 
-from .cabi import DuckEnvConfig, DuckModelDesc, DuckRefMotion
+from .cabi import HEADERS
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DUCK_LIB") or os.path.join(HERE, "libduck.so")
@@ -19,65 +19,19 @@ ROOT = os.path.dirname(HERE)
 
 BUILD = os.path.join(HERE, "build")  # libraries compiled for other models (model_library)
 
-EXPORTS = ["duck_version", "duck_build_id", "duck_last_error", "duck_layout_get", "duck_aux_size", "duck_create", "duck_destroy",
-           "duck_debug_stage_cycles", "duck_model_fingerprint", "duck_model_supported",
-           "duck_reset", "duck_step", "duck_randomize", "duck_physics_step", "duck_gae", "duck_ppo_loss",
-           "duck_ppo_loss_out_size", "duck_mlp_gemm", "duck_mlp_wgrad", "duck_mlp_wgrad_reduce",
-           "duck_policy_sample", "duck_clip_adam", "duck_clip_adam_scratch_size", "duck_set_step_mode",
-           "duck_step_kernel_for", "duck_debug_lat_timeouts", "duck_gather_columns", "duck_mlp_group",
-           "duck_device_error", "duck_gae_stats", "duck_ppo_loss_stats", "duck_mlp_group_bn", "duck_gather_columns_norm",
-           "duck_column_stats", "duck_column_stats_scratch", "duck_clip_adam_reduce", "duck_ppo_loss_grad",
-           "duck_ppo_loss_sums", "duck_mlp_group_tiles", "duck_policy_act", "duck_episode_accumulate",
-           "duck_fleet_observe", "duck_fleet_actuate", "duck_fleet_disturb"]
-
-
-class DuckMlpProblem(C.Structure):
-    """include/duck_ppo.h duck_mlp_problem"""
-    _fields_ = [("kind", C.c_int), ("N", C.c_int), ("R", C.c_int), ("M", C.c_int),
-                ("A", C.c_void_p), ("W", C.c_void_p), ("bias", C.c_void_p), ("aux", C.c_void_p),
-                ("Y", C.c_void_p), ("Y2", C.c_void_p), ("mean", C.c_void_p), ("istd", C.c_void_p),
-                ("splits", C.c_int), ("P", C.c_int), ("off_w", C.c_int), ("off_b", C.c_int), ("partial", C.c_void_p)]
-
-
-class DuckGatherField(C.Structure):
-    """include/duck_ppo.h duck_gather_field"""
-    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("T", C.c_int), ("B", C.c_int), ("w", C.c_int)]
-
-
-FLEET_MAX_NU = 16
-
-
-class DuckFleetDesc(C.Structure):
-    """include/duck_fleet.h duck_fleet_desc"""
-    _fields_ = [("nq", C.c_int), ("nv", C.c_int), ("nu", C.c_int), ("naux", C.c_int), ("sens_off", C.c_int),
-                ("con_off", C.c_int), ("gyro", C.c_int), ("accelerometer", C.c_int), ("upvector", C.c_int),
-                ("local_linvel", C.c_int), ("act_qpos", C.c_int * FLEET_MAX_NU), ("act_dof", C.c_int * FLEET_MAX_NU),
-                ("act_default", C.c_float * FLEET_MAX_NU), ("foot_con", C.c_int * 2), ("dof_vel_scale", C.c_float),
-                ("action_scale", C.c_float), ("accel_x_offset", C.c_float), ("target_step", C.c_float),
-                ("nb_steps_in_period", C.c_int), ("standing", C.c_int), ("speed_limits", C.c_int)]
-
-
-FLEET_PUSH_SIZE = 6
-
-
-class DuckFleetDisturbance(C.Structure):
-    """include/duck_fleet.h duck_fleet_disturbance"""
-    _fields_ = [("seed", C.c_uint64), ("n_sched", C.c_int), ("n_seg", C.c_int), ("seg_periods", C.c_int),
-                ("noise_scale", C.c_float * (17 + 6 * FLEET_MAX_NU))]
+# include/*.h through cabi.HEADERS: the structs, the limits and the declared entry points
+DuckLayout = HEADERS.structs["duck_layout"]
+DuckMlpProblem = HEADERS.structs["duck_mlp_problem"]
+DuckGatherField = HEADERS.structs["duck_gather_field"]
+DuckFleetDesc = HEADERS.structs["duck_fleet_desc"]
+DuckFleetDisturbance = HEADERS.structs["duck_fleet_disturbance"]
+FLEET_MAX_NU = HEADERS.consts["DUCK_FLEET_MAX_NU"]
+FLEET_PUSH_SIZE = HEADERS.consts["DUCK_FLEET_PUSH_SIZE"]
+EXPORTS = list(HEADERS.funcs)
 
 
 class DuckError(RuntimeError):
     pass
-
-
-class DuckLayout(C.Structure):
-    _fields_ = [(k, C.c_int) for k in (
-        "nq", "nv", "nu", "imitation", "task", "obs_size", "priv_size",
-        "qpos", "qvel", "qacc_warmstart", "ctrl", "command", "last_act", "last_last_act", "last_last_last_act",
-        "motor_targets", "feet_air_time", "last_contact", "swing_peak", "push", "action_history", "imu_history",
-        "ref_motion", "imitation_phase", "metrics", "reward", "done", "truncation", "first_qpos", "first_qvel",
-        "first_qacc_warmstart", "first_ctrl", "first_obs", "first_priv", "nfloat",
-        "rng_key", "rng_ctr", "step", "push_step", "push_interval", "imitation_i", "ep_steps", "nint")]
 
 
 # the machine scheduler's max-ILP strategy: the step kernel runs one wave per SIMD, so
@@ -283,78 +237,10 @@ def lib(path: str = None):
         if not os.path.exists(path):
             raise DuckError(f"{path} not built; run __graft_entry__.build() or native.build()")
         L = C.CDLL(path)
-        vp = C.c_void_p
-        L.duck_version.restype = C.c_int
-        L.duck_build_id.restype = C.c_char_p
-        L.duck_last_error.restype = C.c_char_p
-        L.duck_layout_get.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DuckLayout)]
-        L.duck_aux_size.argtypes = [vp]
-        L.duck_create.argtypes = [C.POINTER(DuckModelDesc), C.POINTER(DuckEnvConfig), C.POINTER(DuckRefMotion), C.c_int,
-                                  C.POINTER(vp)]
-        L.duck_destroy.argtypes = [vp]
-        L.duck_destroy.restype = None
-        L.duck_reset.argtypes = [vp, C.c_int, vp, vp, vp, C.c_uint64, C.c_int64, vp, vp, vp, vp]
-        L.duck_step.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.duck_randomize.argtypes = [vp, C.c_int, vp, C.c_uint64, C.c_int64, vp]
-        L.duck_physics_step.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp]
-        L.duck_model_fingerprint.restype = C.c_uint64
-        L.duck_model_fingerprint.argtypes = [C.POINTER(DuckModelDesc)]
-        L.duck_model_supported.argtypes = [C.POINTER(DuckModelDesc)]
-        if hasattr(L, "duck_set_step_mode"):  # (libraries built before the latency kernel: A/B baselines)
-            L.duck_set_step_mode.argtypes = [vp, C.c_int]
-            L.duck_step_kernel_for.argtypes = [vp, C.c_int]
-            L.duck_debug_lat_timeouts.argtypes = [vp, C.POINTER(C.c_uint), C.c_int]
-        if hasattr(L, "duck_device_error"):
-            L.duck_device_error.argtypes = [vp, C.POINTER(C.c_uint), C.c_int]
-        if hasattr(L, "duck_gae"):
-            L.duck_gae.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp, vp, vp]
-        if hasattr(L, "duck_gae_stats"):
-            L.duck_gae_stats.argtypes = [C.c_int, C.c_int, vp, vp, vp, C.c_float, vp, vp, C.c_float, C.c_float, vp, vp,
-                                         C.c_int, vp, vp]
-            L.duck_ppo_loss_stats.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp,
-                                              vp, vp, vp, vp]
-        if hasattr(L, "duck_ppo_loss"):
-            L.duck_ppo_loss.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, C.c_int,
-                                        vp, vp, vp, vp]
-            L.duck_ppo_loss_out_size.argtypes = [C.c_int]
-        if hasattr(L, "duck_mlp_group"):
-            L.duck_mlp_group.argtypes = [C.c_int, C.POINTER(DuckMlpProblem), vp]
-        if hasattr(L, "duck_mlp_group_bn"):
-            L.duck_mlp_group_bn.argtypes = [C.c_int, C.POINTER(DuckMlpProblem), C.c_int, vp]
-        if hasattr(L, "duck_mlp_group_tiles"):
-            L.duck_mlp_group_tiles.argtypes = [C.c_int, C.POINTER(DuckMlpProblem), C.c_int, C.c_int, vp]
-        if hasattr(L, "duck_gather_columns_norm"):
-            L.duck_gather_columns_norm.argtypes = [C.c_int, C.POINTER(DuckGatherField), C.POINTER(C.c_void_p), vp,
-                                                   C.c_int, vp]
-        if hasattr(L, "duck_clip_adam_reduce"):
-            L.duck_clip_adam_reduce.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float,
-                                                C.c_float, C.c_float, C.c_float, vp]
-            L.duck_ppo_loss_grad.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp,
-                                             vp, vp, vp, vp]
-            L.duck_ppo_loss_sums.argtypes = [C.c_int, C.c_int, C.c_float, vp, vp]
-        if hasattr(L, "duck_column_stats"):
-            L.duck_column_stats.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp]
-            L.duck_column_stats_scratch.argtypes = [C.c_int, C.c_int]
-        if hasattr(L, "duck_episode_accumulate"):
-            L.duck_episode_accumulate.argtypes = [C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
-        if hasattr(L, "duck_fleet_observe"):
-            L.duck_fleet_observe.argtypes = [C.POINTER(DuckFleetDesc), C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
-            L.duck_fleet_actuate.argtypes = [C.POINTER(DuckFleetDesc), C.c_int, vp, vp, vp, vp]
-            L.duck_fleet_disturb.argtypes = [C.POINTER(DuckFleetDesc), C.POINTER(DuckFleetDisturbance), C.c_int,
-                                             C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp]
-        if hasattr(L, "duck_gather_columns"):
-            L.duck_gather_columns.argtypes = [C.c_int, C.POINTER(DuckGatherField), vp, C.c_int, vp]
-        if hasattr(L, "duck_mlp_gemm"):
-            ci = C.c_int
-            L.duck_mlp_gemm.argtypes = [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-            L.duck_mlp_wgrad.argtypes = [ci, ci, ci, vp, vp, vp, vp, ci, vp, ci, ci, ci, vp]
-            L.duck_mlp_wgrad_reduce.argtypes = [ci, ci, vp, vp, vp]
-            L.duck_policy_sample.argtypes = [ci, ci, vp, C.c_uint64, vp, vp, vp, vp, vp]
-            if hasattr(L, "duck_policy_act"):
-                L.duck_policy_act.argtypes = [ci, ci, C.POINTER(ci), C.POINTER(vp), C.POINTER(vp), vp, vp, vp, vp, vp, vp]
-            cf = C.c_float
-            L.duck_clip_adam.argtypes = [ci, vp, vp, vp, vp, vp, vp, cf, cf, cf, cf, cf, vp]
-            L.duck_clip_adam_scratch_size.argtypes = [ci]
+        # argtypes and restype of every function the headers declare and this library exports. A declared
+        # function may be absent: a model's own library (model_library, debug_library) links duck_capi.hip
+        # and its variants only; the learner and policy entry points ship with libduck.so.
+        HEADERS.bind(L)
         _libs[path] = L
     return _libs[path]
 

@@ -32,6 +32,8 @@ import torch.distributed as dist
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .cabi import HEADERS
+
 
 @dataclass
 class PPOConfig:
@@ -1091,8 +1093,10 @@ def train(env, cfg: PPOConfig, progress_fn: Optional[Callable[[int, dict], None]
     return result
 
 
-POLICY_ACT_MAX_LAYERS, POLICY_ACT_MAX_WIDTH = 4, 512   # duck_policy_act (include/duck_ppo.h)
-EPISODE_EVAL, EPISODE_TRAIN = 0, 1                      # duck_episode_accumulate's modes
+# duck_policy_act's limits and duck_episode_accumulate's modes (include/duck_ppo.h). The width limit is a literal:
+# it exists only as MAXW in csrc/duck_policy.hip and in the header's comment, not as a #define.
+POLICY_ACT_MAX_LAYERS, POLICY_ACT_MAX_WIDTH = HEADERS.consts["DUCK_POLICY_MAX_LAYERS"], 512
+EPISODE_EVAL, EPISODE_TRAIN = HEADERS.consts["DUCK_EPISODE_EVAL"], HEADERS.consts["DUCK_EPISODE_TRAIN"]
 
 
 def _mean_std(s: float, ss: float, n: int):

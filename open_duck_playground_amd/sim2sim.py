@@ -30,11 +30,31 @@ import numpy as np
 import torch
 
 from . import constants
-from .cabi import dr_layout
+from .cabi import HEADERS, dr_layout
 from .joystick import Joystick
 from .onnx_infer import OnnxInfer
 
 USE_MOTOR_SPEED_LIMITS = True  # mujoco_infer.py:14
+CON_PER_PAIR = HEADERS.consts["DUCK_CON_PER_PAIR"]   # con_dist slots of a collision pair
+
+
+def aux_fields(m) -> Dict[str, Tuple[int, int]]:
+    """(first row, rows) of each field of duck_physics_step's aux record, in write_aux's order
+    (csrc/duck_physics.h; duck_aux_size rows in all)."""
+    out, o = {}, 0
+    for k, n in (("qacc", m.nv), ("qacc_smooth", m.nv), ("qvel", m.nv), ("qfrc_smooth", m.nv),
+                 ("actuator_force", m.nu), ("sensordata", m.nsensordata), ("con_dist", CON_PER_PAIR * m.npair)):
+        out[k] = (o, n)
+        o += n
+    return out
+
+
+def foot_con_slots(m) -> List[int]:
+    """The first con_dist slot of the (floor, foot) pair of each foot in constants.FEET_GEOMS; a pair has
+    CON_PER_PAIR slots."""
+    floor = m.id("geom", "floor")
+    pairs = [{int(m.pair_geom1[k]), int(m.pair_geom2[k])} for k in range(m.npair)]
+    return [CON_PER_PAIR * pairs.index({floor, m.id("geom", foot)}) for foot in constants.FEET_GEOMS]
 
 
 class MjInfer:
@@ -63,12 +83,8 @@ class MjInfer:
         names = m.names["sensor"]
         self.gyro_addr = int(m.sensor_adr[names.index("gyro")])
         self.accelerometer_addr = int(m.sensor_adr[names.index("accelerometer")])
-        floor = m.id("geom", "floor")
-        self._foot_slots = []
-        for foot in constants.FEET_GEOMS:  # the pairs (floor, foot): 4 contact slots each
-            g = m.id("geom", foot)
-            p = [k for k in range(m.npair) if {int(m.pair_geom1[k]), int(m.pair_geom2[k])} == {floor, g}][0]
-            self._foot_slots.append(slice(4 * p, 4 * p + 4))
+        self._foot_slots = [slice(s, s + CON_PER_PAIR) for s in foot_con_slots(m)]
+        self._aux_fields = aux_fields(m)
         key = m.names["key"].index("home")
         self.default_actuator = m.key_ctrl[key].copy()
         self.motor_targets = self.default_actuator.copy()
@@ -98,15 +114,8 @@ class MjInfer:
         self._aux_np = self.aux[:, 0].cpu().numpy().astype(np.float64)
 
     def _aux(self, name: str) -> np.ndarray:
-        m = self.model
-        sizes = [("qacc", m.nv), ("qacc_smooth", m.nv), ("qvel", m.nv), ("qfrc_smooth", m.nv),
-                 ("actuator_force", m.nu), ("sensordata", m.nsensordata), ("con_dist", 4 * m.npair)]
-        o = 0
-        for k, n in sizes:
-            if k == name:
-                return self._aux_np[o:o + n]
-            o += n
-        raise KeyError(name)
+        o, n = self._aux_fields[name]
+        return self._aux_np[o:o + n]
 
     def get_gyro(self) -> np.ndarray:
         return self._aux("sensordata")[self.gyro_addr:self.gyro_addr + 3].copy()
@@ -175,6 +184,11 @@ COMMANDS_RANGE_Y = (-0.2, 0.2)
 COMMANDS_RANGE_THETA = (-1.0, 1.0)
 
 
+def fleet_obs_size(nu: int) -> int:
+    """DUCK_FLEET_OBS_SIZE(nu): the width of the deployment loop's observation."""
+    return HEADERS.value(f"DUCK_FLEET_OBS_SIZE({int(nu)})")
+
+
 def ctl_fields(nu: int) -> Dict[str, Tuple[int, int]]:
     """(first column, width) of each field of the per-robot control record (include/duck_fleet.h)."""
     return {"last_action": (0, nu), "last_last_action": (nu, nu), "last_last_last_action": (2 * nu, nu),
@@ -191,8 +205,8 @@ def fleet_desc(m, naux: int, nb_steps_in_period: int, standing: bool, speed_limi
         raise DuckError(f"the fleet kernels take at most {FLEET_MAX_NU} actuators, the model has {m.nu}")
     d = DuckFleetDesc()
     d.nq, d.nv, d.nu, d.naux = int(m.nq), int(m.nv), int(m.nu), int(naux)
-    d.sens_off = 4 * m.nv + m.nu          # write_aux (csrc/duck_physics.h): qacc, qacc_smooth, qvel,
-    d.con_off = d.sens_off + m.nsensordata  # qfrc_smooth, actuator_force, sensordata, con_dist
+    aux = aux_fields(m)
+    d.sens_off, d.con_off = aux["sensordata"][0], aux["con_dist"][0]
     names = m.names["sensor"]
     for field, sensor in (("gyro", constants.GYRO_SENSOR), ("accelerometer", constants.ACCELEROMETER_SENSOR),
                           ("upvector", constants.GRAVITY_SENSOR), ("local_linvel", constants.LOCAL_LINVEL_SENSOR)):
@@ -201,10 +215,7 @@ def fleet_desc(m, naux: int, nb_steps_in_period: int, standing: bool, speed_limi
     for a, j in enumerate(m.actuator_trnid):
         d.act_qpos[a], d.act_dof[a] = int(m.jnt_qposadr[j]), int(m.jnt_dofadr[j])
         d.act_default[a] = float(m.key_ctrl[key][a])
-    floor = m.id("geom", "floor")
-    for f, foot in enumerate(constants.FEET_GEOMS):   # the pairs (floor, foot): 4 contact slots each
-        g = m.id("geom", foot)
-        d.foot_con[f] = 4 * [k for k in range(m.npair) if {int(m.pair_geom1[k]), int(m.pair_geom2[k])} == {floor, g}][0]
+    d.foot_con[:] = foot_con_slots(m)
     d.dof_vel_scale, d.action_scale, d.accel_x_offset = 0.05, 0.25, 1.3
     d.target_step = float(np.float32(5.24 * 0.002 * 10))
     d.nb_steps_in_period = int(nb_steps_in_period)
@@ -269,7 +280,7 @@ class FleetInfer:
         naux = self.env.aux_size()
         self.desc = fleet_desc(m, naux, nb, standing)
         nu = self.num_dofs = int(m.nu)
-        self.obs_size = 17 + 6 * nu
+        self.obs_size = fleet_obs_size(nu)
 
         # the policy's dense layers on the device, pointers in host arrays (duck_policy_act's arguments)
         if sizes[0] != self.obs_size or pol["action_size"] != nu:
@@ -288,8 +299,8 @@ class FleetInfer:
         self.warm, self.ctrl, self.aux = z(m.nv, n), z(nu, n), z(naux, n)
         self._scratch = z(n * m.nv * m.nv)
         self.fields = ctl_fields(nu)
-        self.ctl, self.obs, self.action = z(n, 5 * nu + 11), z(n, self.obs_size), z(n, nu)
-        self.acc, self.alive = z(n, 6), torch.ones(n, dtype=torch.float32, device=dev)
+        self.ctl, self.obs, self.action = z(n, HEADERS.value(f"DUCK_FLEET_CTL_SIZE({nu})")), z(n, self.obs_size), z(n, nu)
+        self.acc, self.alive = z(n, HEADERS.consts["DUCK_FLEET_ACC_SIZE"]), torch.ones(n, dtype=torch.float32, device=dev)
         self.dr = None
         if randomize is not None:
             self.dr = z(dr_layout(m.nbody, nu)["nfloat"] * n)
@@ -607,7 +618,7 @@ def default_noise_scales(nu: int, dof_vel_scale: float = 0.05) -> np.ndarray:
     from . import config
     cfg = config.default_config()
     sc = cfg.noise_config.scales
-    out = np.zeros(17 + 6 * nu)
+    out = np.zeros(fleet_obs_size(nu))
     out[0:3], out[3:6] = sc.gyro, sc.accelerometer
     out[13:13 + nu] = config.qpos_noise_scale(cfg, max(nu, len(constants.JOINTS_ORDER_NO_HEAD)))[:nu]
     out[13 + nu:13 + 2 * nu] = sc.joint_vel * dof_vel_scale

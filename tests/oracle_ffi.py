@@ -13,6 +13,7 @@ from typing import Optional
 
 import numpy as np
 
+from open_duck_playground_amd import cabi, cdecl
 from open_duck_playground_amd.cabi import (DuckEnvConfig, DuckRefMotion, ModelDescHolder, dr_layout, layout,
                                            refmotion_struct)
 from open_duck_playground_amd.mjcf import Model
@@ -21,29 +22,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # ORACLE_LIB selects another build of the same checker (oracle/Makefile ASAN=1: liboracle_asan.so)
 LIB = os.environ.get("ORACLE_LIB") or os.path.join(ROOT, "oracle", "liboracle.so")
 
-MAXQ, MAXV, MAXU, MAXSD, MAXBODY, MAXSITE, MAXGEOM, MAXCON = 40, 32, 16, 64, 20, 8, 64, 16
+# oracle/duck_oracle.h on top of the product's headers (the same struct classes): oracle_data, the prototypes
+HEADERS = cdecl.Header(os.path.join(ROOT, "oracle", "duck_oracle.h"), base=cabi.HEADERS)
+MAXQ, MAXV, MAXU, MAXSD, MAXBODY, MAXSITE, MAXGEOM, MAXCON = (
+    HEADERS.consts["DUCK_MAX" + k] for k in ("Q", "V", "U", "SENSORDATA", "BODY", "SITE", "GEOM", "CON"))
 
 
-class OracleData(C.Structure):
-    _fields_ = [
-        ("qpos", C.c_double * MAXQ), ("qvel", C.c_double * MAXV), ("qacc_warmstart", C.c_double * MAXV),
-        ("ctrl", C.c_double * MAXU),
-        ("qacc", C.c_double * MAXV), ("qacc_smooth", C.c_double * MAXV), ("qfrc_smooth", C.c_double * MAXV),
-        ("qfrc_bias", C.c_double * MAXV), ("qfrc_passive", C.c_double * MAXV), ("qfrc_actuator", C.c_double * MAXV),
-        ("qfrc_constraint", C.c_double * MAXV),
-        ("actuator_force", C.c_double * MAXU),
-        ("sensordata", C.c_double * MAXSD),
-        ("xpos", C.c_double * 3 * MAXBODY), ("xquat", C.c_double * 4 * MAXBODY), ("xmat", C.c_double * 9 * MAXBODY),
-        ("xipos", C.c_double * 3 * MAXBODY), ("ximat", C.c_double * 9 * MAXBODY),
-        ("site_xpos", C.c_double * 3 * MAXSITE), ("site_xmat", C.c_double * 9 * MAXSITE),
-        ("geom_xpos", C.c_double * 3 * MAXGEOM), ("geom_xmat", C.c_double * 9 * MAXGEOM),
-        ("qM", C.c_double * MAXV * MAXV),
-        ("ncon", C.c_int),
-        ("con_dist", C.c_double * MAXCON), ("con_pos", C.c_double * 3 * MAXCON), ("con_frame", C.c_double * 9 * MAXCON),
-        ("con_geom1", C.c_int * MAXCON), ("con_geom2", C.c_int * MAXCON),
-        ("nefc", C.c_int), ("efc_force", C.c_double * 128), ("solver_niter", C.c_int),
-    ]
-
+class OracleData(HEADERS.structs["oracle_data"]):
     def arr(self, name, n=None):
         a = np.ctypeslib.as_array(getattr(self, name))
         return a if n is None else a[:n]
@@ -65,49 +50,9 @@ def lib():
     if _lib is None:
         build()
         L = C.CDLL(LIB)
-        vp = C.c_void_p
-        L.oracle_model_create.restype = vp
-        L.oracle_model_create.argtypes = [C.c_void_p]
-        L.oracle_model_destroy.argtypes = [vp]
-        L.oracle_model_randomized.restype = vp
-        L.oracle_model_randomized.argtypes = [vp, C.POINTER(C.c_double)]
-        L.oracle_dr_sample.argtypes = [vp, C.c_uint64, C.c_int64, C.POINTER(C.c_double)]
-        L.oracle_forward.argtypes = [vp, C.POINTER(OracleData)]
-        L.oracle_step.argtypes = [vp, C.POINTER(OracleData), C.c_int]
-        L.oracle_threefry2x32.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-        L.oracle_env_reset.argtypes = [vp, C.POINTER(DuckEnvConfig), C.POINTER(DuckRefMotion), C.c_uint64, C.c_int64,
-                                       dp, ip, dp, dp]
-        L.oracle_env_step.argtypes = [vp, C.POINTER(DuckEnvConfig), C.POINTER(DuckRefMotion), dp, ip, dp, dp, dp, dp,
-                                      dp, C.POINTER(OracleData)]
-        L.oracle_set_trace.argtypes = [dp]
-        L.oracle_set_ls_floor.argtypes = [C.c_double]
-        L.oracle_ls_trace.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        L.oracle_set_force_start.argtypes = [C.c_int]
-        L.oracle_set_hdump.argtypes = [dp]
-        L.oracle_set_hf_band_scale.argtypes = [C.c_double]
-        L.oracle_get_hf_band_scale.restype = C.c_double
-        L.oracle_set_hf_defect.argtypes = [C.c_int, C.c_double]
-        L.oracle_get_hf_defect.argtypes = [C.c_int]
-        L.oracle_get_hf_defect.restype = C.c_double
-        L.oracle_hfield_select.argtypes = [dp, dp, dp, C.c_int, ip]
+        HEADERS.bind(L)   # argtypes and restype of every function duck_oracle.h declares
         if os.environ.get("ORACLE_HF_BAND_SCALE"):  # A/B of a kernel built with -DDUCK_HF_POINT_BAND=...
             L.oracle_set_hf_band_scale(float(os.environ["ORACLE_HF_BAND_SCALE"]))
-        L.oracle_set_hf_tie_last.argtypes = [C.c_double]
-        L.oracle_set_hf_tie_first.argtypes = [C.c_double]
-        L.oracle_hfield_contacts.argtypes = [vp, C.POINTER(OracleData), C.c_int, C.c_int, C.c_int, dp, dp, dp]
-        L.oracle_set_con_override.argtypes = [dp]
-        L.oracle_last_start_costs.argtypes = [C.POINTER(C.c_double)]
-        L.oracle_hfield_axis_wins.argtypes = [C.POINTER(C.c_longlong), C.c_int]
-        L.oracle_hfield_prisms.argtypes = [vp, C.POINTER(OracleData), C.c_int, C.c_int, C.c_int, dp, dp, dp, ip]
-        L.oracle_reference_motion.argtypes = [C.POINTER(DuckRefMotion), C.c_double, C.c_double, C.c_double, C.c_int, dp]
-        L.oracle_reward_imitation.restype = C.c_double
-        L.oracle_reward_imitation.argtypes = [dp, dp, dp, dp, dp, dp, dp, C.c_int]
-        L.oracle_rewards.argtypes = [dp, dp, dp, dp, dp, dp, dp, dp, dp, C.c_int, C.c_double, dp]
-        L.oracle_batch_step.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(DuckEnvConfig), C.POINTER(DuckRefMotion),
-                                        C.c_int, dp, ip, dp, dp, dp, dp, dp, C.c_int]
-        L.oracle_batch_reset.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(DuckEnvConfig), C.POINTER(DuckRefMotion),
-                                         C.c_int, C.c_uint64, C.c_int64, dp, ip, dp, dp, C.c_int]
         _lib = L
     return _lib
 
