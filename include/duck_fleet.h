@@ -14,7 +14,8 @@
  *   duck_fleet_actuate  the action history, motor targets, speed limit and ctrl (mujoco_infer.py:208-231)
  *
  * and, only when the caller disturbs the loop as the training env does (noise, changing commands, pushes),
- * duck_fleet_disturb between duck_fleet_observe and duck_policy_act.
+ * duck_fleet_disturb between duck_fleet_observe and duck_policy_act; and, only when the caller keeps a flight
+ * recorder, duck_fleet_record after duck_fleet_actuate.
  *
  * The entries are model-agnostic: a host descriptor filled from the compiled model tells them where
  * the sensors, the actuated joints and the foot contacts are. Conventions are duck.h's: DEVICE
@@ -147,6 +148,47 @@ typedef struct {
 int duck_fleet_disturb(const duck_fleet_desc* desc, const duck_fleet_disturbance* dis, int N, int64_t robot_offset,
                        int32_t* tick, const float* sched, const int32_t* sched_id, const float* push, float* qvel,
                        float* ctl, float* obs, void* stream);
+
+/* The flight recorder: a ring of the last `depth` control periods per robot that freezes when the robot
+ * falls, so that a fall is still there to be looked at after the run (the reference keeps what its loop saw
+ * for the same purpose: saved_obs, mujoco_infer.py:202, :241). One more launch, enqueued last in the period,
+ * after duck_fleet_actuate; a loop without a recorder does not enqueue it. All of its state is on the device
+ * (head, after), so that a captured graph replays it.
+ *
+ * ring [N][depth][F] row-major float32, F = DUCK_FLEET_FRAME_SIZE(nq, nv, nu): a robot's ring is contiguous
+ * and a frame is F consecutive words, in this order:
+ *   qpos            nq                       qpos[k][e]
+ *   qvel            nv                       qvel[k][e]; a push duck_fleet_disturb applied for the next period
+ *                                            is already in it
+ *   qacc_warmstart  nv                       warm[k][e]
+ *   ctl             DUCK_FLEET_CTL_SIZE(nu)  the control record after duck_fleet_actuate
+ *   obs             DUCK_FLEET_OBS_SIZE(nu)  what the policy saw, the noise included
+ *   action          nu                       duck_policy_act's output, action [N][nu]
+ *   actuator_force  nu                       aux rows 4 nv + a (write_aux's order, see duck_fleet_desc)
+ *   sensors         DUCK_FLEET_SENS_SIZE     aux rows sens_off + gyro, accelerometer, upvector, local_linvel
+ *                                            (3 each, in this order; raw: no offset, no noise)
+ * That is the loop's whole input for the next period (qpos, qvel, qacc_warmstart, ctl; ctrl is not stored:
+ * it equals ctl.motor_targets bit for bit) and what the robot sensed and did in this one. Words are copied,
+ * never computed: NaN payloads, -0 and denormals keep their bits.
+ *
+ * For robot e, with dead = (alive[e] == 0): when dead and after[e] >= post + 1 the robot is frozen and
+ * nothing of it is written. Otherwise the frame is written at slot head[e] % depth, head[e] += 1, and when
+ * dead, after[e] += 1. So a robot that never falls holds its last min(head, depth) periods, oldest at slot
+ * head % depth once head >= depth; one that falls holds the periods up to the one in which
+ * duck_fleet_observe cleared alive (the fall frame) and `post` more (post = 0: the ring ends at the fall
+ * frame); one that was dead before the first call writes post + 1 frames. head, after [N] int32, zeroed by
+ * the caller; a frame carries no stamp: the j-th call (from 1) since the counters were zeroed wrote the frame
+ * that head counted as its j-th, for every robot not yet frozen.
+ *
+ * desc gives nq, nv, nu, naux and the sensor addresses; DUCK_EINVAL on depth < 1, post < 0, a sensor address
+ * outside the aux record (duck_fleet_observe's checks) or 4 nv + nu > naux. N == 0 launches nothing. */
+#define DUCK_FLEET_SENS_SIZE 12
+/* nq + 2 nv + CTL(nu) + OBS(nu) + 2 nu + 12, written out so the macro uses its arguments only */
+#define DUCK_FLEET_FRAME_SIZE(nq, nv, nu) ((nq) + 2 * (nv) + 13 * (nu) + 40)
+
+int duck_fleet_record(const duck_fleet_desc* desc, int N, int depth, int post, const float* qpos, const float* qvel,
+                      const float* warm, const float* aux, const float* ctl, const float* obs, const float* action,
+                      const float* alive, int32_t* head, int32_t* after, float* ring, void* stream);
 
 #ifdef __cplusplus
 }

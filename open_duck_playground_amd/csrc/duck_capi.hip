@@ -297,6 +297,60 @@ __global__ __launch_bounds__(FLEET_TPB) void fleet_disturb_kernel(const duck_fle
   }
 }
 
+// The flight recorder (include/duck_fleet.h: duck_fleet_record), the same 16-lane group per robot. The lanes
+// stride over the frame's words: word k's source is found by walking the fields in the frame's order; the SoA
+// rows are read next to the neighbouring groups', the robot's own rows and the frame in runs of 16 consecutive
+// words. Words travel as uint32_t: a copy, whatever the bits. Every lane of a group loads head, after and alive
+// (one broadcast load each), so the frozen exit is taken by the whole group; lane 0 stores the two counters at
+// the end, after the wave's loads of them (fleet_disturb_kernel's argument for tick). No LDS, no votes: lanes
+// past the last robot leave.
+__global__ __launch_bounds__(FLEET_TPB) void fleet_record_kernel(
+    const duck_fleet_desc D, int n, int depth, int post, const uint32_t* __restrict__ qpos,
+    const uint32_t* __restrict__ qvel, const uint32_t* __restrict__ warm, const uint32_t* __restrict__ aux,
+    const uint32_t* __restrict__ ctl, const uint32_t* __restrict__ obs, const uint32_t* __restrict__ action,
+    const float* __restrict__ alive, int* head, int* after, uint32_t* __restrict__ ring) {
+  const int lane = threadIdx.x % FLEET_TEAM;
+  const int e0 = blockIdx.x * (FLEET_TPB / FLEET_TEAM) + threadIdx.x / FLEET_TEAM;
+  if (e0 >= n) return;
+  const size_t e = e0, N = n;
+  const int h = head[e], af = after[e];
+  const bool dead = alive[e] == 0.f;
+  if (dead && af > post) return;  // frozen
+  const int nq = D.nq, nv = D.nv, nu = D.nu, C = DUCK_FLEET_CTL_SIZE(nu), O = DUCK_FLEET_OBS_SIZE(nu);
+  const int F = DUCK_FLEET_FRAME_SIZE(nq, nv, nu);
+  // (unsigned: a head the caller did not zero, or one past 2^31 calls, still lands inside the robot's ring)
+  uint32_t* frame = ring + (e * (size_t)depth + (size_t)((unsigned)h % (unsigned)depth)) * F;
+  for (int k = lane; k < F; k += FLEET_TEAM) {
+    uint32_t v;
+    int j = k;
+    if (j < nq) {
+      v = qpos[(size_t)j * N + e];
+    } else if ((j -= nq) < nv) {
+      v = qvel[(size_t)j * N + e];
+    } else if ((j -= nv) < nv) {
+      v = warm[(size_t)j * N + e];
+    } else if ((j -= nv) < C) {
+      v = ctl[e * C + j];
+    } else if ((j -= C) < O) {
+      v = obs[e * O + j];
+    } else if ((j -= O) < nu) {
+      v = action[e * nu + j];
+    } else if ((j -= nu) < nu) {
+      v = aux[(size_t)(4 * nv + j) * N + e];  // actuator_force
+    } else {
+      j -= nu;
+      const int s = j / 3;
+      const int adr = s == 0 ? D.gyro : s == 1 ? D.accelerometer : s == 2 ? D.upvector : D.local_linvel;
+      v = aux[(size_t)(D.sens_off + adr + j % 3) * N + e];
+    }
+    frame[k] = v;
+  }
+  if (lane == 0) {
+    head[e] = h + 1;
+    if (dead) after[e] = af + 1;
+  }
+}
+
 static const char* fleet_desc_error(const duck_fleet_desc* d) {
   if (d->nq < 1 || d->nv < 1 || d->nu < 1 || d->nu > DUCK_FLEET_MAX_NU) return "nq, nv >= 1 and 1 <= nu <= 16";
   for (int a = 0; a < d->nu; a++)
@@ -378,6 +432,32 @@ int duck_fleet_disturb(const duck_fleet_desc* d, const duck_fleet_disturbance* d
   const int per = FLEET_TPB / FLEET_TEAM;
   hipLaunchKernelGGL(fleet_disturb_kernel, dim3((n + per - 1) / per), dim3(FLEET_TPB), 0, (hipStream_t)stream, *dis,
                      d->nu, noisy, n, (long long)robot_offset, tick, sched, sched_id, push, qvel, ctl, obs);
+  HIPCHECK(hipGetLastError());
+  return DUCK_OK;
+}
+
+int duck_fleet_record(const duck_fleet_desc* d, int n, int depth, int post, const float* qpos, const float* qvel,
+                      const float* warm, const float* aux, const float* ctl, const float* obs, const float* action,
+                      const float* alive, int32_t* head, int32_t* after, float* ring, void* stream) {
+  g_err.clear();
+  if (!d || !qpos || !qvel || !warm || !aux || !ctl || !obs || !action || !alive || !head || !after || !ring)
+    return duck_fail(DUCK_EINVAL, "duck_fleet_record: null pointer");
+  if (n < 0 || n > (1 << 27)) return duck_fail(DUCK_EINVAL, "duck_fleet_record: bad size (0 <= N <= 2^27)");
+  if (depth < 1 || post < 0) return duck_fail(DUCK_EINVAL, "duck_fleet_record: depth >= 1 and post >= 0");
+  if (const char* why = fleet_desc_error(d)) return duck_fail(DUCK_EINVAL, std::string("duck_fleet_record: ") + why);
+  // every aux row the kernel reads lies inside the record
+  const int sensors[4] = {d->gyro, d->accelerometer, d->upvector, d->local_linvel};
+  for (int s : sensors)
+    if (s < 0 || d->sens_off < 0 || (long long)d->sens_off + s + 3 > d->naux)
+      return duck_fail(DUCK_EINVAL, "duck_fleet_record: sensor address outside the aux record");
+  if (4LL * d->nv + d->nu > d->naux)
+    return duck_fail(DUCK_EINVAL, "duck_fleet_record: actuator_force rows (4 nv + nu) outside the aux record");
+  if (n == 0) return DUCK_OK;
+  const int per = FLEET_TPB / FLEET_TEAM;
+  hipLaunchKernelGGL(fleet_record_kernel, dim3((n + per - 1) / per), dim3(FLEET_TPB), 0, (hipStream_t)stream, *d, n,
+                     depth, post, (const uint32_t*)qpos, (const uint32_t*)qvel, (const uint32_t*)warm,
+                     (const uint32_t*)aux, (const uint32_t*)ctl, (const uint32_t*)obs, (const uint32_t*)action, alive,
+                     head, after, (uint32_t*)ring);
   HIPCHECK(hipGetLastError());
   return DUCK_OK;
 }

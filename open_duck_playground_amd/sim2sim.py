@@ -18,7 +18,10 @@ user has of an exported policy -- does it track commands over the whole command 
 randomised models -- takes thousands of runs. ``python -m open_duck_playground_amd.sim2sim`` keeps the
 reference's flags and adds ``--num_robots``, ``--periods``, ``--command_grid``, ``--randomize``, ``--out``, and the
 disturbances the training env has and the reference's deployment loop lacks: ``--push_grid``, ``--push_at``,
-``--push_every``, ``--recovery_window``, ``--noise``, ``--noise_seed``, ``--resample_commands``.
+``--push_every``, ``--push_magnitude``, ``--recovery_window``, ``--noise``, ``--noise_seed``,
+``--resample_commands``; and the flight recorder, ``--record_falls``, ``--record_post``, ``--record_out``,
+``--record_max``: the last periods of every robot that fell, written to an ``.npz`` (the reference keeps what
+its loop saw in ``saved_obs``; the file holds the same observations and the state around them).
 """
 
 from __future__ import annotations
@@ -197,6 +200,33 @@ def ctl_fields(nu: int) -> Dict[str, Tuple[int, int]]:
             "imitation_phase": (5 * nu + 9, 2)}
 
 
+FRAME_SENSORS = ("gyro", "accelerometer", "upvector", "local_linvel")   # the order inside a frame's "sensors"
+
+
+def frame_fields(nq: int, nv: int, nu: int) -> Dict[str, Tuple[int, int]]:
+    """(first word, width) of each field of a recorded frame, in the frame's order (include/duck_fleet.h
+    duck_fleet_record; DUCK_FLEET_FRAME_SIZE(nq, nv, nu) words in all). ``ctl`` is the whole control record
+    (``ctl_fields``), ``sensors`` the four raw sensors of ``FRAME_SENSORS``, 3 words each."""
+    out, o = {}, 0
+    for k, n in (("qpos", nq), ("qvel", nv), ("qacc_warmstart", nv), ("ctl", HEADERS.value(f"DUCK_FLEET_CTL_SIZE({int(nu)})")),
+                 ("obs", fleet_obs_size(nu)), ("action", nu), ("actuator_force", nu),
+                 ("sensors", HEADERS.consts["DUCK_FLEET_SENS_SIZE"])):
+        out[k] = (o, int(n))
+        o += int(n)
+    assert o == HEADERS.value(f"DUCK_FLEET_FRAME_SIZE({int(nq)},{int(nv)},{int(nu)})")
+    return out
+
+
+def unroll_ring(ring_row, head: int, depth: int, rec_base: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    """One robot's ring in period order. ``ring_row`` [depth][F] (or flat), ``head`` the frames the robot has
+    written: the last min(head, depth) of them are held, the j-th written (from 1) at slot (j - 1) % depth.
+    Returns (frames [T][F] oldest first, period [T] = rec_base + j)."""
+    depth, head = int(depth), int(head)
+    ring_row = np.asarray(ring_row).reshape(depth, -1)
+    j = np.arange(max(head - depth, 0), head, dtype=np.int64)        # j - 1 of the frames still held
+    return ring_row[j % depth], int(rec_base) + j + 1
+
+
 def fleet_desc(m, naux: int, nb_steps_in_period: int, standing: bool, speed_limits: bool = USE_MOTOR_SPEED_LIMITS):
     """duck_fleet_desc (include/duck_fleet.h) of a compiled model: where the deployment loop's sensors,
     actuated joints and foot contacts are, and the loop's constants (mujoco_infer.py:27-31, :58, :74)."""
@@ -244,14 +274,24 @@ class FleetInfer:
     configured, a period is physics -> observe -> duck_fleet_disturb -> policy -> actuate, the fifth launch
     adding sensor noise to the observation, writing the next period's command and pushing the base before
     the next period's physics. The period count ``tick`` lives on the device, so a captured graph replays it.
-    With none configured the loop is the four launches above, unchanged."""
+    With none configured the loop is the four launches above, unchanged. ``robot_offset`` is the global id of
+    robot 0 in the disturbance stream (a robot's draws depend on the seed, its global id and the period only).
 
-    CHUNK = 50   # control periods per captured graph (200 launches, 250 with disturbances)
+    The flight recorder (off by default; ``set_recorder(depth, post)`` or ``recorder=(depth, post)``): one more
+    launch at the end of the period, duck_fleet_record, keeps every robot's last ``depth`` periods in a ring on
+    the device -- the state the next period starts from, the control record, the observation the policy saw,
+    its action, the actuator forces and the raw sensors -- and freezes a robot's ring ``post`` periods after
+    the one in which it fell. Its counters live on the device, so it runs inside the captured graph.
+    ``recorded(robot)`` returns the frames in period order; ``replay(robot, frame)`` returns a one-robot fleet
+    loaded from a recorded frame, whose next periods reproduce the robot's bit for bit."""
+
+    CHUNK = 50   # control periods per captured graph (200 launches; 250 with disturbances; 50 more with a recorder)
 
     def __init__(self, model_path: str = "flat_terrain", onnx_model_path: Optional[str] = None, num_robots: int = 1,
                  reference_data: Optional[str] = None, standing: bool = False, device="cuda:0",
                  randomize: Optional[int] = None, command_schedule: Optional[tuple] = None,
-                 pushes: Optional[tuple] = None, noise: Optional[tuple] = None):
+                 pushes: Optional[tuple] = None, noise: Optional[tuple] = None, recorder: Optional[tuple] = None,
+                 robot_offset: int = 0):
         import ctypes as C
 
         from .native import DuckError, check
@@ -313,6 +353,13 @@ class FleetInfer:
         self.tick = torch.zeros(n, dtype=torch.int32, device=dev)
         self.dis = DuckFleetDisturbance()
         self.sched = self.sched_id = self.push = None
+        self.robot_offset = int(robot_offset)
+        # the flight recorder (include/duck_fleet.h duck_fleet_record): off
+        self.frame_fields = frame_fields(int(m.nq), int(m.nv), nu)
+        self.ring = self.rec_head = self.rec_after = None
+        self.rec_depth = self.rec_post = self.rec_base = self.periods_done = 0
+        self._made_from = dict(model_path=model_path, onnx_model_path=onnx_model_path, reference_data=reference_data,
+                               standing=standing, device=device)
         self.restart()
         if command_schedule is not None:
             self.set_command_schedule(*command_schedule)
@@ -320,12 +367,14 @@ class FleetInfer:
             self.set_pushes(*pushes)
         if noise is not None:
             self.set_noise(*noise)
+        if recorder is not None:
+            self.set_recorder(*recorder)
 
     def restart(self) -> None:
         """Every robot back to the loop's start, with the randomisation record ``dr`` as it is now.
         MJInferBase.__init__: MjData at qpos0 with zero ctrl, one mj_step, then the home keyframe's qpos and
         ctrl (the velocity of that first step is kept); mujoco_infer.py:49-60 for the control record. The
-        period count goes back to 0 and a command schedule to its segment 0."""
+        period count goes back to 0, a command schedule to its segment 0, and a recorder to no frames."""
         m, n = self.model, self.num_robots
         col = lambda a: torch.tensor(np.asarray(a, dtype=np.float32)[:, None], device=self.device)  # noqa: E731
         key = m.names["key"].index("home")
@@ -342,6 +391,10 @@ class FleetInfer:
         self.tick.zero_()
         self._schedule_command()   # segment 0 of a schedule, if one is set
         self.reset_report()
+        self.periods_done = self.rec_base = 0
+        if self.ring is not None:
+            self.rec_head.zero_()
+            self.rec_after.zero_()
 
     # --- launches -----------------------------------------------------------------------------
     def _stream(self):
@@ -383,12 +436,23 @@ class FleetInfer:
         import ctypes as C
         L = self._lib
         ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        self._check(L.duck_fleet_disturb(C.byref(self.desc), C.byref(self.dis), self.num_robots, 0, self.tick.data_ptr(),
-                                         ptr(self.sched), ptr(self.sched_id), ptr(self.push), self.qvel.data_ptr(),
-                                         self.ctl.data_ptr(), self.obs.data_ptr(), self._stream()), L)
+        self._check(L.duck_fleet_disturb(C.byref(self.desc), C.byref(self.dis), self.num_robots, self.robot_offset,
+                                         self.tick.data_ptr(), ptr(self.sched), ptr(self.sched_id), ptr(self.push),
+                                         self.qvel.data_ptr(), self.ctl.data_ptr(), self.obs.data_ptr(),
+                                         self._stream()), L)
+
+    def record(self):
+        """duck_fleet_record: this period's frame into the ring of every robot not yet frozen."""
+        import ctypes as C
+        L = self._lib
+        self._check(L.duck_fleet_record(C.byref(self.desc), self.num_robots, self.rec_depth, self.rec_post,
+                                        self.qpos.data_ptr(), self.qvel.data_ptr(), self.warm.data_ptr(),
+                                        self.aux.data_ptr(), self.ctl.data_ptr(), self.obs.data_ptr(),
+                                        self.action.data_ptr(), self.alive.data_ptr(), self.rec_head.data_ptr(),
+                                        self.rec_after.data_ptr(), self.ring.data_ptr(), self._stream()), L)
 
     def _periods(self, k: int, rec: Optional[torch.Tensor] = None, t0: int = 0):
-        disturbed = self.disturbed()
+        disturbed, recording = self.disturbed(), self.ring is not None
         for t in range(k):
             self._physics(self.decimation)
             self.observe()
@@ -397,6 +461,8 @@ class FleetInfer:
             if rec is not None:
                 rec[t0 + t].copy_(self.obs)
             self.act()
+            if recording:
+                self.record()
 
     @torch.no_grad()
     def run(self, n_periods: int, record: bool = False):
@@ -406,6 +472,7 @@ class FleetInfer:
         n_periods = int(n_periods)
         rec = torch.empty(n_periods, self.num_robots, self.obs_size, device=self.device) if record else None
         self.calls += 1
+        self.periods_done += n_periods
         chunk = max(1, int(self.CHUNK))
         if record or self.calls == 1 or n_periods < chunk:
             self._periods(n_periods, rec)
@@ -549,6 +616,81 @@ class FleetInfer:
         for k in range(self.obs_size):
             self.dis.noise_scale[k] = float(eff[k])
 
+    # --- the flight recorder (include/duck_fleet.h duck_fleet_record) ----------------------------------
+    def set_recorder(self, depth: Optional[int], post: int = 0) -> None:
+        """Keep every robot's last ``depth`` control periods on the device, frozen ``post`` periods after the
+        one in which the robot fell (0: the ring ends at the fall frame). A new, empty ring: the frame written
+        by the j-th period run from now on is period ``rec_base + j``, with ``rec_base`` the periods run since
+        ``restart()``. ``depth=None`` turns the recorder off. [N][depth][F] float32 on the device (232 MB
+        for 4,096 robots of the shipped model at depth 50)."""
+        from .native import DuckError
+        self.graph = None
+        if depth is None:
+            self.ring = self.rec_head = self.rec_after = None
+            self.rec_depth = self.rec_post = 0
+            return
+        if int(depth) != depth or int(depth) < 1 or int(post) != post or int(post) < 0 or max(depth, post) >= 2 ** 31 - 1:
+            raise DuckError(f"a recorder needs integers depth >= 1 and post >= 0, got {depth!r}, {post!r}")
+        n, F = self.num_robots, sum(w for _, w in self.frame_fields.values())
+        self.rec_depth, self.rec_post, self.rec_base = int(depth), int(post), self.periods_done
+        self.ring = torch.zeros(n, self.rec_depth, F, dtype=torch.float32, device=self.device)
+        self.rec_head = torch.zeros(n, dtype=torch.int32, device=self.device)
+        self.rec_after = torch.zeros(n, dtype=torch.int32, device=self.device)
+
+    def _frames(self, robot: int) -> Tuple[np.ndarray, np.ndarray]:
+        from .native import DuckError
+        if self.ring is None:
+            raise DuckError("no recorder is set (set_recorder)")
+        if not 0 <= int(robot) < self.num_robots:
+            raise DuckError(f"robot must lie in [0, {self.num_robots}), got {robot!r}")
+        torch.cuda.synchronize(self.device)
+        return unroll_ring(self.ring[int(robot)].cpu().numpy(), int(self.rec_head[int(robot)]), self.rec_depth, self.rec_base)
+
+    def recorded(self, robot: int) -> Dict[str, np.ndarray]:
+        """Robot ``robot``'s recorded frames, oldest first: ``"period"`` [T] (1-based, counted from
+        ``restart()``), every field of ``frame_fields`` by name as [T][width] float32, and ``"fell"``. A robot
+        that fell holds the periods up to the one in which it fell and ``post`` more; one that did not, the
+        last ``depth``."""
+        frames, period = self._frames(robot)
+        out = {"period": period, "fell": bool(self.alive[int(robot)] == 0)}
+        for name, (o, w) in self.frame_fields.items():
+            out[name] = np.ascontiguousarray(frames[:, o:o + w])
+        return out
+
+    def replay(self, robot: int, frame: int = 0) -> "FleetInfer":
+        """A one-robot fleet that continues robot ``robot`` from its recorded frame ``frame`` (an index into
+        ``recorded(robot)``; negative from the newest): the same model, policy, ``standing`` flag and noise,
+        the robot's randomisation record, schedule and push row, and its global id in the disturbance stream.
+        The loop is a pure function of what a frame holds, that record and that stream, so running the replay
+        k periods reproduces the k periods the robot ran after that frame, bit for bit. The fleet's settings
+        are taken as they are now: they must not have changed since the frame was written."""
+        from .native import DuckError
+        frames, period = self._frames(robot)
+        if not -len(frames) <= int(frame) < len(frames):
+            raise DuckError(f"robot {robot} holds {len(frames)} frames, got frame {frame!r}")
+        robot = int(robot)
+        f, p = torch.tensor(frames[int(frame)], device=self.device), int(period[int(frame)])
+        r = FleetInfer(num_robots=1, randomize=None if self.dr is None else 0,
+                       robot_offset=self.robot_offset + robot, **self._made_from)
+        if self.dr is not None:
+            r.dr.copy_(self.dr.view(-1, self.num_robots)[:, robot])
+        # the disturbances first, the frame last: set_command_schedule writes a command
+        r.set_noise(1.0, int(self.dis.seed), np.array(self.dis.noise_scale[:self.obs_size], dtype=np.float64))
+        if self.sched is not None:
+            r.set_command_schedule(self.sched.cpu().numpy(), [int(self.sched_id[robot])], int(self.dis.seg_periods))
+        if self.push is not None:
+            r.set_pushes(0)
+            r.push.copy_(self.push[robot:robot + 1])
+        part = lambda name: f[self.frame_fields[name][0]:][:self.frame_fields[name][1]]  # noqa: E731
+        for dst, name in ((r.qpos, "qpos"), (r.qvel, "qvel"), (r.warm, "qacc_warmstart")):
+            dst[:, 0].copy_(part(name))
+        r.ctl[0].copy_(part("ctl"))
+        r.ctrl[:, 0].copy_(r.ctl_field("motor_targets")[0])
+        if self.disturbed():   # the device's period count at that frame: it has advanced once per period since
+            r.tick.copy_(self.tick[robot:robot + 1] - (self.periods_done - p))
+        r.periods_done = p
+        return r
+
     def state(self):
         """(qpos [N][nq], qvel [N][nv], ctrl [N][nu]) as numpy float32."""
         return tuple(t.t().contiguous().cpu().numpy() for t in (self.qpos, self.qvel, self.ctrl))
@@ -683,6 +825,8 @@ def push_report(rep: Dict[str, np.ndarray], push_cells: np.ndarray, first, inter
 def add_disturbance_arguments(p) -> None:
     p.add_argument("--push_grid", type=str, default=None, metavar="NMxND",
                    help="NM push magnitudes over push_config.magnitude_range x ND directions over [0, 2 pi)")
+    p.add_argument("--push_magnitude", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                   help="the push grid's magnitude range in m/s (default: push_config.magnitude_range)")
     p.add_argument("--push_at", type=int, default=100, metavar="PERIOD", help="the first push (>= 1)")
     p.add_argument("--push_every", type=int, default=0, metavar="PERIODS", help="repeat the push (0 = once)")
     p.add_argument("--recovery_window", type=int, default=100, metavar="PERIODS",
@@ -706,7 +850,10 @@ def disturbance_plan(args, cells: np.ndarray):
     plan = {"schedule": None, "pushes": None, "push_cells": None, "push_cell": None}
     echo = {"push_grid": args.push_grid, "noise": args.noise, "noise_seed": args.noise_seed,
             "resample_commands": args.resample_commands}
-    pcells = push_grid(args.push_grid) if args.push_grid is not None else np.zeros((1, 2), np.float32)
+    magnitude = getattr(args, "push_magnitude", None)
+    if magnitude is not None and not (np.isfinite(magnitude).all() and 0 <= magnitude[0] <= magnitude[1]):
+        raise ValueError("--push_magnitude wants finite 0 <= LO <= HI")
+    pcells = push_grid(args.push_grid, magnitude) if args.push_grid is not None else np.zeros((1, 2), np.float32)
     ccell, pcell = robot_cells(n, len(cells), len(pcells))
     if args.push_grid is not None:
         if args.push_at < 1:
@@ -714,6 +861,8 @@ def disturbance_plan(args, cells: np.ndarray):
         plan["pushes"] = (args.push_at, args.push_every, pcells[pcell, 0], pcells[pcell, 1])
         plan["push_cells"], plan["push_cell"] = pcells, pcell
         echo.update(push_at=args.push_at, push_every=args.push_every, recovery_window=args.recovery_window)
+        if magnitude is not None:
+            echo["push_magnitude"] = [float(v) for v in magnitude]
     if args.resample_commands:
         plan["schedule"] = (resample_schedule(cells, args.periods, args.resample_commands), ccell.astype(np.int32),
                             args.resample_commands)
@@ -721,9 +870,41 @@ def disturbance_plan(args, cells: np.ndarray):
     return plan
 
 
-def main(argv=None) -> int:
-    import argparse
+def add_recorder_arguments(p) -> None:
+    p.add_argument("--record_falls", type=int, default=None, metavar="DEPTH",
+                   help="keep every robot's last DEPTH periods on the device, frozen at its fall")
+    p.add_argument("--record_post", type=int, default=0, metavar="K", help="periods kept after the fall frame")
+    p.add_argument("--record_out", type=str, default=None, metavar="falls.npz",
+                   help="write the fallen robots' frames (needs --record_falls)")
+    p.add_argument("--record_max", type=int, default=64, metavar="R", help="at most R robots, lowest ids first")
+
+
+def falls_archive(fleet: "FleetInfer", max_robots: int) -> Dict[str, np.ndarray]:
+    """The arrays of the command line's ``--record_out`` file: the frames of the fallen robots, lowest ids
+    first and at most ``max_robots`` of them. ``robots`` [R], ``count`` [R] (frames held), ``survived`` [R] (the
+    report's periods survived: the robot fell in the next one), ``period`` [R][depth] (-1 past ``count``), every field of ``frame_fields`` as [R][depth][width] (zero past
+    ``count``), and ``fields``: the field map {name: [first word, width]} as a JSON string."""
     import json
+    rep = fleet.report()
+    fell = np.flatnonzero(rep["fell"])[:max(0, int(max_robots))]
+    depth = fleet.rec_depth
+    out = {"robots": fell.astype(np.int64), "count": np.zeros(len(fell), np.int64),
+           "survived": rep["periods"][fell].astype(np.int64),
+           "period": np.full((len(fell), depth), -1, np.int64)}
+    for name, (_, w) in fleet.frame_fields.items():
+        out[name] = np.zeros((len(fell), depth, w), np.float32)
+    for k, robot in enumerate(fell):
+        rec = fleet.recorded(int(robot))
+        t = out["count"][k] = len(rec["period"])
+        out["period"][k, :t] = rec["period"]
+        for name in fleet.frame_fields:
+            out[name][k, :t] = rec[name]
+    out["fields"] = np.array(json.dumps({k: list(v) for k, v in fleet.frame_fields.items()}))
+    return out
+
+
+def build_parser():
+    import argparse
     p = argparse.ArgumentParser(description="Run an exported policy in the deployment loop for a fleet of robots")
     p.add_argument("-o", "--onnx_model_path", type=str, required=True)
     p.add_argument("--reference_data", type=str, default=None)
@@ -736,7 +917,24 @@ def main(argv=None) -> int:
     p.add_argument("--out", type=str, default=None, metavar="report.json")
     p.add_argument("--device", type=str, default="cuda:0")
     add_disturbance_arguments(p)
+    add_recorder_arguments(p)
+    return p
+
+
+def parse_arguments(argv=None):
+    """The command line's arguments; a flag that needs another one is a usage error."""
+    p = build_parser()
     args = p.parse_args(argv)
+    if args.record_falls is None and args.record_out is not None:
+        p.error("--record_out needs --record_falls DEPTH")
+    if args.record_falls is not None and (args.record_falls < 1 or args.record_post < 0 or args.record_max < 0):
+        p.error("--record_falls wants DEPTH >= 1, --record_post K >= 0 and --record_max R >= 0")
+    return args
+
+
+def main(argv=None) -> int:
+    import json
+    args = parse_arguments(argv)
     cells = command_grid(args.command_grid)
     plan = disturbance_plan(args, cells)
     fleet = FleetInfer(args.model_path, args.onnx_model_path, args.num_robots, reference_data=args.reference_data,
@@ -749,6 +947,8 @@ def main(argv=None) -> int:
             fleet.set_pushes(*plan["pushes"])
         if args.noise:
             fleet.set_noise(args.noise, args.noise_seed)
+    if args.record_falls is not None:
+        fleet.set_recorder(args.record_falls, args.record_post)
     t0 = time.time()
     fleet.run(args.periods)
     dt = time.time() - t0
@@ -764,6 +964,14 @@ def main(argv=None) -> int:
                                         args.recovery_window)
             for row in doc["pushes"]:
                 row["magnitude"], row["theta"] = (float(v) for v in plan["push_cells"][row["cell"]])
+    if args.record_falls is not None:
+        written = 0
+        if args.record_out:
+            arrays = falls_archive(fleet, args.record_max)
+            np.savez(args.record_out, **arrays)
+            written = int(len(arrays["robots"]))
+        doc["recorder"] = {"depth": args.record_falls, "post": args.record_post, "fallen": int(rep["fell"].sum()),
+                           "written": written}
     text = json.dumps(doc, indent=1)
     if args.out:
         with open(args.out, "w") as f:
