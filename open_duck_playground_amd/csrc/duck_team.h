@@ -101,6 +101,18 @@ DK void team_for(int lane, F&& f) {
     if (B0 + TEAM * (s + 1) <= N || i < N) f(i);
   }
 }
+// the same items with every lane running every slice: f(i, ok), where a lane past N gets item 0 and
+// ok = false and sends its stores to its sink slots (L[ok ? addr : TLay::SINK + lane]) -- no exec-masked
+// region around the last slice (its save, its execz branch and its restore; tools/isa_exec_regions.py)
+template <int N, class F>
+DK void team_all(int lane, F&& f) {
+#pragma unroll
+  for (int s = 0; s < (N + TEAM - 1) / TEAM; s++) {
+    const int i = lane + TEAM * s;
+    const bool ok = TEAM * (s + 1) <= N || i < N;
+    f(ok ? i : 0, ok);
+  }
+}
 DK float tmaxf(float v) {
   v = fmaxf(v, dppf<0xB1>(v));
   v = fmaxf(v, dppf<0x4E>(v));
@@ -857,11 +869,11 @@ struct TPhys {
     // tip (the limb bodies are compile-time, Md::T_BRB), then the limb totals, then the root path.
     // Each component's additions run in the same order as a limb-per-lane pass.
     subtree_sums<PART>(L, lane);
-    team_for<NV>(lane, [&](int i) {
+    team_all<NV>(lane, [&](int i, bool ok) {
       const int b = dof_body(i);
       float s = 0.0f;
       for (int k = 0; k < 6; k++) s += L[Ly::CDOF + 6 * i + k] * L[TL::CFRC + 6 * b + k];
-      L[Ly::FSM + i] = -s;
+      L[ok ? Ly::FSM + i : TL::SINK + lane] = -s;
     });
     TSYNC();
   }
@@ -1065,19 +1077,23 @@ struct TPhys {
 #pragma unroll
     for (int s = 0; s < NVS; s++) {
       const int i = lane + TEAM * s;
-      if (TEAM * (s + 1) <= NV || i < NV) L[Ly::FSM + i] = P.fsm[s] + -P.damp[s] * P.qv[s];
+      // (lanes past NV store to their sink slot: no lane-guarded region, see TL::SINK)
+      L[TEAM * (s + 1) <= NV || i < NV ? Ly::FSM + i : TL::SINK + lane] = P.fsm[s] + -P.damp[s] * P.qv[s];
     }
     TSYNC();
-    if (lane < NU) {
-      const int a = lane;
+    {
+      // every lane runs the actuator it loaded (lanes past NU: actuator 0, smooth_pre) and the lanes past NU
+      // store to their sink slots
+      const bool act = lane < NU;
       float c = P.c;
       if (P.clim) c = fminf(fmaxf(c, P.clo), P.chi);
       const float g = P.g, kp = P.kp;
       const float len = g * P.qp, vel = g * P.qd;
       float f = kp * c + (-kp * len - P.kv * vel);
       if (P.flim) f = fminf(fmaxf(f, P.flo), P.fhi);
-      L[Ly::AF + a] = f;
-      L[Ly::FSM + P.dof] += g * f;
+      const float fs = L[Ly::FSM + P.dof];
+      L[act ? Ly::AF + lane : TL::SINK + lane] = f;
+      L[act ? Ly::FSM + P.dof : TL::SINK + TEAM + lane] = fs + g * f;
     }
     TSYNC();
   }
@@ -3613,15 +3629,15 @@ struct TPhys {
       if (typ == 7 && site == Md::LFOOT_SITE) L[Ly::FOOTZ] = sp[2];
       if (typ == 7 && site == Md::RFOOT_SITE) L[Ly::FOOTZ + 1] = sp[2];
     }
-    if (lane < 2) {
+    {
       // (compile-time table entries selected by lane: indexed by lane, the tables were read from
-      // global memory with an exposed load)
+      // global memory with an exposed load; lanes past 1 work the second pair and store to their sink slot)
       constexpr int p0 = Md::PLANE_PAIR[0], p1 = Md::PLANE_PAIR[1];
       constexpr int s20 = cgeom_slot<Md>(Md::pair_geom2[p0]), s21 = cgeom_slot<Md>(Md::pair_geom2[p1]);
       const int p = lane == 0 ? p0 : p1, s2 = lane == 0 ? s20 : s21;
       float mn = 1e4f;
       for (int c = 0; c < 4; c++) mn = fminf(mn, L[Ly::CDIST + 4 * p + c]);
-      L[Ly::OCON + s2 - 1] = mn < 0.0f ? 1.0f : 0.0f;
+      L[lane < 2 ? Ly::OCON + s2 - 1 : TL::SINK + lane] = mn < 0.0f ? 1.0f : 0.0f;
     }
     TSYNC();
   }
@@ -3629,13 +3645,18 @@ struct TPhys {
   // ---------------- semi-implicit Euler ----------------
   static DK void euler(LP L, int lane) {
     const float dt = Md::timestep;
-    team_for<NV>(lane, [&](int i) {
-      L[Ly::WARM + i] = L[Ly::QACC + i];
-      L[Ly::QVEL + i] += dt * L[Ly::QACC + i];
+    team_all<NV>(lane, [&](int i, bool ok) {
+      const float qa = L[Ly::QACC + i], qv = L[Ly::QVEL + i];
+      L[ok ? Ly::WARM + i : TL::SINK + lane] = qa;
+      L[ok ? Ly::QVEL + i : TL::SINK + TEAM + lane] = qv + dt * qa;
     });
     TSYNC();
-    if (lane == 0) {
-      for (int k = 0; k < 3; k++) L[Ly::QPOS + k] += dt * L[Ly::QVEL + k];
+    {
+      // the free joint, on every lane from the same words: each lane holds the same result and the team
+      // stores it unguarded (same word, same value: such writes cost no more than lane 0's alone,
+      // tools/exec_region_probe.hip form e); the loads are issued ahead of the stores
+      float qp[3];
+      for (int k = 0; k < 3; k++) qp[k] = L[Ly::QPOS + k] + dt * L[Ly::QVEL + k];
       const float v[3] = {L[Ly::QVEL + 3], L[Ly::QVEL + 4], L[Ly::QVEL + 5]};
       const float nvv = sqrtf(dot3(v, v));
       float ax[3] = {1.0f, 0.0f, 0.0f};
@@ -3646,6 +3667,7 @@ struct TPhys {
       float q[4] = {L[Ly::QPOS + 3], L[Ly::QPOS + 4], L[Ly::QPOS + 5], L[Ly::QPOS + 6]};
       qmul(q, q, qr);
       qnormalize(q);
+      for (int k = 0; k < 3; k++) L[Ly::QPOS + k] = qp[k];
       for (int k = 0; k < 4; k++) L[Ly::QPOS + 3 + k] = q[k];
     }
     team_for<NJ, 1>(lane, [&](int j) {
