@@ -21,6 +21,7 @@ from __future__ import annotations
 
 import contextlib
 import os
+from collections import Counter
 from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional
 
@@ -52,6 +53,8 @@ class Report:
     reset: dict = field(default_factory=dict)  # the strict post-reset comparison (reset_stats)
     env: object = None
     models: object = None
+    unwrapped: object = None   # makes the same env without the training wrappers (run(); None when there are none)
+    _twin: object = None       # that env and its buffers, made on first use (unrestored_step)
 
     def outliers(self, s: StepStats) -> np.ndarray:
         bad = np.zeros_like(s.done_mismatch)
@@ -96,14 +99,28 @@ def _fs_err(L, fa, fb, n):
     return out
 
 
+def oracle_batch(m: Model, cfg, n: int, seed: int, dr: bool):
+    """The oracle side of a run: one OracleModel (or, with domain randomisation, one per env drawn from
+    ``seed + 1``, the wrappers' DR seed), and the OracleBatch over them after its reset from ``seed``.
+    Shared by run() and tests/late_states.py's harvest, which has no GPU env to take m and cfg from."""
+    base = OracleModel(m)
+    models = [OracleModel(m, dr=base.dr_sample(seed + 1, e)) for e in range(n)] if dr else base
+    ob = OracleBatch(models, cfg, n)
+    ob.reset(seed=seed)
+    return models, ob
+
+
 def run(task: str, imitation: bool, n: int, steps: int, device, seed: int = 7, dr: bool = False,
         auto_reset: bool = False, episode_length: int = 1000, overrides: Optional[dict] = None,
         force_push: bool = False, force_resample: bool = False, env_cls=Joystick, action_seed: int = 0,
         keep_states: bool = False, oracle_edit: Optional[Callable[[Model], Model]] = None,
-        step_mode: str = "auto") -> Report:
+        step_mode: str = "auto", pre_states: Optional[list] = None) -> Report:
     """``oracle_edit`` hands the oracle a deliberately wrong model (a copy of the GPU's, edited; the
     GPU keeps the nominal one): the injected-defect test of ``explain`` (DEFECTS). ``step_mode``:
-    Joystick.set_step_mode ("auto" runs the latency kernel at these batch sizes, <= 4 envs per CU)."""
+    Joystick.set_step_mode ("auto" runs the latency kernel at these batch sizes, <= 4 envs per CU).
+    ``pre_states``: a list of (fs, is_, actions), one per step (tests/late_states.py's mosaics): step t
+    writes that state into the oracle batch before the fp32 rounding and the upload, and takes its
+    actions instead of drawing them."""
     kw = {} if env_cls is not Joystick else {"use_imitation": imitation}
     env = env_cls(task, num_envs=n, device=device, config_overrides=overrides, **kw)
     if auto_reset:
@@ -112,20 +129,26 @@ def run(task: str, imitation: bool, n: int, steps: int, device, seed: int = 7, d
     elif dr:
         domain_randomize(env, rng=seed + 1)
     env.set_step_mode(step_mode)
+
+    def unwrapped():
+        twin = env_cls(task, num_envs=n, device=device, config_overrides=overrides, **kw)
+        if dr:
+            domain_randomize(twin, rng=seed + 1)
+        twin.set_step_mode(step_mode)
+        return twin
     st = env.reset(rng=seed)
     om_model = oracle_edit(copy_model(env.mj_model)) if oracle_edit is not None else env.mj_model
-    base = OracleModel(om_model)
-    models = [OracleModel(om_model, dr=base.dr_sample(seed + 1, e)) for e in range(n)] if dr else base
     cfg = env._cfg_struct                      # the exact struct duck_create received
     L = env._layout
-    ob = OracleBatch(models, cfg, n)
-    ob.reset(seed=seed)
+    models, ob = oracle_batch(om_model, cfg, n, seed, dr)
     rng = np.random.default_rng(action_seed)
-    rep = Report(tol=default_tol(), env=env, models=models)
+    rep = Report(tol=default_tol(), env=env, models=models, unwrapped=unwrapped if auto_reset else None)
     torch.cuda.synchronize()
     rep.reset = reset_stats(L, st, ob, n)
     I = lambda name: L.ioff[name]  # noqa: E731
     for t in range(steps):
+        if pre_states is not None:
+            ob.fs[:], ob.is_[:] = pre_states[t][0], pre_states[t][1]
         isv = ob.is_.reshape(L.nint, n)
         if t == 0 and force_push:        # every third env pushed on this step (push_step+1 == interval)
             sel = np.arange(n) % 3 == 0
@@ -137,6 +160,8 @@ def run(task: str, imitation: bool, n: int, steps: int, device, seed: int = 7, d
         st.fstate.copy_(torch.from_numpy(ob.fs.astype(np.float32)))
         st.istate.copy_(torch.from_numpy(ob.is_.copy()))
         a = rng.uniform(-1, 1, (n, env.action_size)).astype(np.float32)
+        if pre_states is not None:
+            a = np.asarray(pre_states[t][2], dtype=np.float32).reshape(n, env.action_size)
         if keep_states:
             rep.pre.append((ob.fs.copy(), ob.is_.copy(), a.copy()))
         st = env.step(st, torch.from_numpy(a).to(st.fstate.device))
@@ -267,6 +292,71 @@ CASES = {
 }
 
 
+# the late-state cases (tests/late_states.py, tests/test_gpu_late_states.py): the training wrappers with
+# the full 1000-step episode, each "step" one mosaic of states harvested from the oracle's own free run
+# (falls, the steps around them, touchdowns, step 60). The last one runs the throughput kernel, the
+# others the latency kernel ("auto" at 256 envs)
+LATE_CASES = {
+    "late_flat": dict(task="flat_terrain", imitation=False),
+    "late_flat_backlash_imitation": dict(task="flat_terrain_backlash", imitation=True),
+    "late_rough_backlash_dr": dict(task="rough_terrain_backlash", imitation=False, dr=True),
+    "late_flat_throughput_kernel": dict(task="flat_terrain", imitation=True, step_mode="throughput"),
+}
+LATE_EPISODE = 1000
+
+
+def run_late_case(name: str, device, **extra) -> Report:
+    """run() over the case's mosaics (late_states.mosaics, in late_states.CLASSES order), 256 envs."""
+    from tests import late_states
+    mos = late_states.mosaics(name)
+    pre = [(mos[c].fs, mos[c].is_, mos[c].act) for c in late_states.CLASSES]
+    h = late_states.harvest(name, late_states.LATE_SEEDS[name])
+    return run(n=h.n, steps=len(pre), device=device, seed=h.seed, auto_reset=True, episode_length=LATE_EPISODE,
+               pre_states=pre, **dict(LATE_CASES[name], **extra))
+
+
+def check_report(case: str, rep: Report, step_names: Optional[List[str]] = None) -> List[dict]:
+    """The teacher-forced bar on a Report: the reset strictly (>= 99.5 % of envs inside reset_stats'
+    bars, the others explained by explain_reset), >= 99.5 % of env-steps inside the bars, and every
+    env-step outside them -- or with a done or integer mismatch -- "sensitive" under explain(). Prints the
+    figures and the explanation rules used; returns the rule counts per step (printed per step under
+    ``step_names``)."""
+    s = rep.summary()
+    print(case, {k: v for k, v in s.items()})
+    # the reset itself, strictly: every fstate row, obs, privileged obs and istate word of every env
+    # at the same bar, >= 99.5 % of envs, and every env outside it explained (explain_reset)
+    r = rep.reset
+    bad = (r["norm"] > 1) | r["int_mismatch"]
+    print(f"  reset: worst err/bar {r['norm'].max():.3f} ({r['worst_row'][r['norm'].argmax()]}), "
+          f"outside the bar {int(bad.sum())}, int mismatches {int(r['int_mismatch'].sum())}")
+    assert bad.mean() <= 0.005, [(int(e), r["worst_row"][e], float(r["norm"][e])) for e in bad.nonzero()[0][:8]]
+    for e in bad.nonzero()[0]:
+        x = explain_reset(rep, int(e))
+        print(f"  reset outlier env {e} ({r['worst_row'][e]}, err/bar {r['norm'][e]:.1f}): {x}")
+        assert x["kind"] == "sensitive", (int(e), x)
+    assert s["good_frac"] >= 0.995, s
+    unexplained = []
+    rules = Counter()
+    per_step = []
+    for t, st in enumerate(rep.steps):
+        out = rep.outliers(st) | st.done_mismatch | st.int_mismatch
+        mine = Counter()
+        for e in out.nonzero()[0]:
+            x = explain(rep, t, int(e))
+            print(f"  outlier step {t} env {e}: {x['kind']} max substep err {max(x['substep_err']):.2e} "
+                  f"flips {x.get('flips')} gpu_flip {x.get('gpu_flip')} chain_vs_step {x.get('chain_vs_step', 0):.2e}")
+            mine.update(rule_of(x))
+            if x["kind"] != "sensitive":
+                unexplained.append((t, int(e), x))
+        rules.update(mine)
+        per_step.append({"outliers": int(out.sum()), "rules": dict(sorted(mine.items()))})
+        if step_names is not None:
+            print(f"  {step_names[t]}: outliers {per_step[-1]['outliers']}, rules {per_step[-1]['rules']}")
+    print(f"  rules: {dict(sorted(rules.items()))}")
+    assert not unexplained, unexplained
+    return per_step
+
+
 def copy_model(m: Model) -> Model:
     return Model(name=m.name, arrays={k: v.copy() for k, v in m.arrays.items()}, names=dict(m.names),
                  hulls=[Hull(vert=h.vert.copy(), face_normal=h.face_normal.copy(), face_offset=h.face_offset.copy(),
@@ -381,14 +471,19 @@ def run_case(name: str, device, n: int = 256, steps: int = 6, **extra) -> Report
 
 def substep_trace(rep: Report, e: int, t: int):
     """The oracle's env-step t of env e with every substep's input state (qpos, qvel,
-    qacc_warmstart, ctrl); row n_substeps is the final state. Needs keep_states=True."""
+    qacc_warmstart, ctrl); row n_substeps is the final state: the step's physics result, also where
+    the env-step ends in done under the training wrappers (whose restore would put the reset snapshot
+    in its place: the oracle runs the step without them here; the physics does not depend on them).
+    Needs keep_states=True."""
     import ctypes as C
     from tests.oracle_ffi import OracleEnv, lib
     env, L = rep.env, rep.env._layout
     m, n = env.mj_model, env.num_envs
     fs, is_, a = rep.pre[t]
     om = rep.models[e] if isinstance(rep.models, list) else rep.models
-    oe = OracleEnv(om, env._cfg_struct)
+    cfg = type(env._cfg_struct).from_buffer_copy(env._cfg_struct)
+    cfg.auto_reset = 0
+    oe = OracleEnv(om, cfg)
     oe.fs[:] = fs.reshape(L.nfloat, n)[:, e]
     oe.is_[:] = is_.reshape(L.nint, n)[:, e]
     tr = np.zeros((env.n_substeps + 1, m.nq + 2 * m.nv + m.nu))
@@ -403,6 +498,34 @@ def substep_trace(rep: Report, e: int, t: int):
     tr[-1, m.nq + m.nv:m.nq + 2 * m.nv] = oe.fs[o["qacc_warmstart"]:o["qacc_warmstart"] + m.nv]
     tr[-1, m.nq + 2 * m.nv:] = tr[-2, m.nq + 2 * m.nv:]
     return om, tr
+
+
+def unrestored_step(rep: Report, t: int) -> np.ndarray:
+    """The GPU's fstate [nfloat, n] after env-step t without the training wrappers' restore. Where an
+    env-step ends in done, the wrapped step's fstate holds the reset snapshot in place of the step's
+    physics result, and explain() would compare its substep chain with the snapshot. The same step
+    kernel takes the step again from the same pre-state in an env made without the wrappers (same
+    model, DR record and step mode; auto_reset is a run-time word of the config): its qpos, qvel and
+    qacc_warmstart are what the wrapped step computed before it restored. Checked here: in every env
+    the wrapped step left running, the two steps' physics rows are the same bits."""
+    env, L, n = rep.env, rep.env._layout, rep.env.num_envs
+    if rep._twin is None:
+        twin = rep.unwrapped()
+        rep._twin = (twin, twin.reset(rng=0), {})
+    twin, st, cache = rep._twin
+    if t not in cache:
+        fs, is_, a = rep.pre[t]
+        st.fstate.copy_(torch.from_numpy(fs.astype(np.float32)))
+        st.istate.copy_(torch.from_numpy(is_.copy()))
+        out = twin.step(st, torch.from_numpy(a).to(st.fstate.device))
+        torch.cuda.synchronize()
+        U = out.fstate.cpu().numpy().astype(np.float64).reshape(L.nfloat, n)
+        G = rep.post[t].reshape(L.nfloat, n)
+        running = G[L.off["done"]] == 0
+        rows = slice(L.off["qpos"], L.off["qacc_warmstart"] + L.nv)
+        assert np.array_equal(U[rows][:, running], G[rows][:, running]), "the step without the wrappers differs"
+        cache[t] = U
+    return cache[t]
 
 
 def _split(m, x):
@@ -750,7 +873,11 @@ def explain(rep: Report, t: int, e: int, sub_tol: float = 1e-4, seed: int = 0) -
     are inlined): the chain's final state must be closer to step_kernel's output than a quarter of
     step_kernel's distance from the oracle (and within 1e-3). Then the env-step difference is the
     oracle's own sensitivity to fp32-sized input differences, amplified over the 10 substeps:
-    "sensitive". Otherwise "defect". Needs keep_states=True."""
+    "sensitive". Otherwise "defect". Needs keep_states=True.
+    An env-step that ends in done under the training wrappers leaves the reset snapshot in fstate on
+    both sides: "step_kernel's output" and the oracle's final state are then the step's physics results
+    before the restore (unrestored_step, substep_trace), or a fall's outlier would be compared with the
+    snapshot -- step_vs_oracle 0, a bar of 0 -- and called a defect whatever the kernel did."""
     env = rep.env
     m = env.mj_model
     om, tr = substep_trace(rep, e, t)
@@ -776,6 +903,9 @@ def explain(rep: Report, t: int, e: int, sub_tol: float = 1e-4, seed: int = 0) -
     L, n = env._layout, env.num_envs
     G = rep.post[t].reshape(L.nfloat, n)[:, e]
     o = L.off
+    if rep.unwrapped is not None and G[o["done"]] != 0:
+        # done under the training wrappers: fstate holds the restored snapshot, not the step's result
+        G = unrestored_step(rep, t)[:, e]
     step_out = np.concatenate([G[o["qpos"]:o["qpos"] + m.nq], G[o["qvel"]:o["qvel"] + m.nv],
                                G[o["qacc_warmstart"]:o["qacc_warmstart"] + m.nv], tr[-1, m.nq + 2 * m.nv:]])
     chain_vs_step = _state_rel(m, x, step_out)

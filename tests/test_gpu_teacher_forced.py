@@ -24,39 +24,10 @@ from collections import Counter
 import numpy as np
 import pytest
 
-from tests.teacher_forcing import CASES, DEFECTS, explain, explain_reset, nominal_agrees, oracle_knob, rule_of, run_case
+from tests.teacher_forcing import CASES, DEFECTS, explain, nominal_agrees, oracle_knob, rule_of, run_case
+from tests.teacher_forcing import check_report as _check  # the bar of this module's docstring, shared with test_gpu_late_states.py
 
 pytestmark = pytest.mark.gpu
-
-
-def _check(case, rep):
-    s = rep.summary()
-    print(case, {k: v for k, v in s.items()})
-    # the reset itself, strictly: every fstate row, obs, privileged obs and istate word of every env
-    # at the same bar, >= 99.5 % of envs, and every env outside it explained (explain_reset)
-    r = rep.reset
-    bad = (r["norm"] > 1) | r["int_mismatch"]
-    print(f"  reset: worst err/bar {r['norm'].max():.3f} ({r['worst_row'][r['norm'].argmax()]}), "
-          f"outside the bar {int(bad.sum())}, int mismatches {int(r['int_mismatch'].sum())}")
-    assert bad.mean() <= 0.005, [(int(e), r["worst_row"][e], float(r["norm"][e])) for e in bad.nonzero()[0][:8]]
-    for e in bad.nonzero()[0]:
-        x = explain_reset(rep, int(e))
-        print(f"  reset outlier env {e} ({r['worst_row'][e]}, err/bar {r['norm'][e]:.1f}): {x}")
-        assert x["kind"] == "sensitive", (int(e), x)
-    assert s["good_frac"] >= 0.995, s
-    unexplained = []
-    rules = Counter()
-    for t, st in enumerate(rep.steps):
-        out = rep.outliers(st) | st.done_mismatch | st.int_mismatch
-        for e in out.nonzero()[0]:
-            x = explain(rep, t, int(e))
-            print(f"  outlier step {t} env {e}: {x['kind']} max substep err {max(x['substep_err']):.2e} "
-                  f"flips {x.get('flips')} gpu_flip {x.get('gpu_flip')} chain_vs_step {x.get('chain_vs_step', 0):.2e}")
-            rules.update(rule_of(x))
-            if x["kind"] != "sensitive":
-                unexplained.append((t, int(e), x))
-    print(f"  rules: {dict(sorted(rules.items()))}")
-    assert not unexplained, unexplained
 
 
 @pytest.mark.parametrize("case", list(CASES))
