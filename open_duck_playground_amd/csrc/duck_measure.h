@@ -240,6 +240,7 @@ static int stage_cycles_of(unsigned long long* out, int reset) {
   D(6, "kinematics") \
   D(7, "com_pos") \
   D(8, "rne + smooth") \
+  D(9, "M's register columns") \
   D(11, "hf SAT pass 2") \
   D(12, "hf SAT pass 1") \
   D(13, "hf contact point") \

@@ -15,6 +15,7 @@
 #pragma once
 #include <utility>
 
+#include "duck_mcols.h"
 #include "duck_physics.h"
 
 constexpr int TEAM = 16;
@@ -957,6 +958,11 @@ struct TPhys {
     // (the composite inertias were summed in rne's subtree pass)
     STAGE_MARK(ST_CRB_SUMS);
     ASM_MARK("CRB_BEGIN");
+    // lane opaque (throughput kernel): the store guards and the armature selects below are lane masks that
+    // do not change from substep to substep; hoisted out of the substep loop they live in SGPR pairs spilled
+    // to VGPR lanes, two v_readlane per use. Formed here each is one compare (C2 +0.7 %, bit-identical;
+    // MCOLS_LEAN: not in the backlash scenes, whose 30 rows in two full-form sets lose by it)
+    if constexpr (MCOLS_LEAN) asm volatile("" : "+v"(lane));
     L[lane == 0 ? Ly::MZERO : TL::SINK + lane] = 0.0f;  // the zero word load_cols reads (LDS is not
                                                           // initialised by the launch)
     // M row i (lane i, i + 16): F_i = crb_{body(i)} cdof_i stays in registers;
@@ -1104,6 +1110,15 @@ struct TPhys {
   // a pass is a handful of broadcasts and FMAs with no memory traffic. Entries above the
   // diagonal may collect garbage; factor_solve zeroes them before the triangular solves.
   static constexpr int NC = (NV + TEAM - 1) / TEAM;
+  // row r of M is zero in every column of set s (no column of the set is r, an ancestor or a descendant of
+  // r; duck_mcols.h): known at compile time from the dof tree. The throughput kernel's M x skips such
+  // entries -- 0 . x_r added to a sum that starts at +0 changes no bit for finite x_r -- and load_cols'
+  // loads of them are then dead (flat: rows 6-14 of set 1, 9 of 40 entries). The latency kernels' code
+  // stays as it is, and so does the throughput kernel's of a scene where the two steps do not pay
+  // (mcols_lean, duck_mcols.h)
+  using MCo = MCols<Md, TEAM>;
+  static constexpr bool MCOLS_LEAN = LAT == 0 && mcols_lean<Md>();
+  static constexpr bool zrow(int r, int s) { return MCOLS_LEAN && MCo::zero_row(r, s); }
   struct Fac {
     float col[NC][NV];
     float dg[NC];
@@ -1235,7 +1250,7 @@ struct TPhys {
   // out of line so the rare dense path does not share the hot path's code layout / registers
   static DNI void newton_dense(LP L, int lane) {
     float Mc[NC][NV];
-    load_cols(L, lane, Mc, false);
+    load_cols(L, lane, Mc);
     newton_fused<true>(L, lane, Mc);
   }
   // dense variant (a full lower triangle): pivots in natural order NV-1 .. 0, each updating every
@@ -1297,9 +1312,9 @@ struct TPhys {
     fwd_all_dense(F, x, lane, std::make_integer_sequence<int, NV>{});
   }
 
-  // columns of the symmetric tree-sparse M: full (both triangles) or lower only. Entries outside
+  // columns of the symmetric tree-sparse M, both triangles. Entries outside
   // the tree pattern (and columns past NV) read the zero word after M: one load per entry, no mask
-  static DK void load_cols(LP L, int lane, float (*col)[NV], bool lower_only) {
+  static DK void load_cols(LP L, int lane, float (*col)[NV]) {
     if constexpr (TL::TAB_LDS) {
       // lane opaque: the table words are per-lane constants, which the compiler would otherwise
       // hoist out of the substep loop and keep in registers (+39 AGPRs)
@@ -1316,14 +1331,9 @@ struct TPhys {
           int a[G];
 #pragma unroll
           for (int r = r0; r < r0 + G && r < NV; r++)
-            if (!(lower_only && r < TEAM * s)) a[r - r0] = ti(Md::B_MCOLZ + TEAM * (NV * s + r) + lane);
+            a[r - r0] = ti(Md::B_MCOLZ + TEAM * (NV * s + r) + lane);
 #pragma unroll
-          for (int r = r0; r < r0 + G && r < NV; r++) {
-            if (lower_only && r < TEAM * s) { col[s][r] = 0.0f; continue; }  // above the diagonal
-            // (with lower_only the entries right of the diagonal may stay: the factorization's lower
-            // triangle never reads them, and factor_solve drops them afterwards)
-            col[s][r] = L[Ly::M + a[r - r0]];
-          }
+          for (int r = r0; r < r0 + G && r < NV; r++) col[s][r] = L[Ly::M + a[r - r0]];
         }
       }
     } else {
@@ -1336,7 +1346,6 @@ struct TPhys {
 #pragma unroll
         for (int r = 0; r < NV; r++) {
           const int a = madr(r, cc);
-          if (lower_only && r < TEAM * s) { col[s][r] = 0.0f; continue; }
           const float v = L[Ly::M + (a >= 0 ? a : 0)];  // unconditional load: no branch per entry
           col[s][r] = (c < NV && a >= 0) ? v : 0.0f;
         }
@@ -1395,10 +1404,16 @@ struct TPhys {
 
   // y = M x for the lane's columns (M held as full columns); Y[c] = y. x[s] holds x_c of the lane's
   // columns c = TEAM s + lane; x_r reaches every lane by a DPP row broadcast folded into the FMA
+  template <int R>
+  static DK void mul_row(const float (*Mc)[NV], const float* x, float* y) {
+    static_for<0, NC>([&](auto ss) {
+      constexpr int S = decltype(ss)::value;
+      if constexpr (!zrow(R, S)) y[S] += Mc[S][R] * bc<R % TEAM>(x[R / TEAM]);
+    });
+  }
   template <int... R>
   static DK void mul_acc(const float (*Mc)[NV], const float* x, float* y, std::integer_sequence<int, R...>) {
-#pragma unroll
-    for (int s = 0; s < NC; s++) ((y[s] += Mc[s][R] * bc<R % TEAM>(x[R / TEAM])), ...);
+    (mul_row<R>(Mc, x, y), ...);
   }
   static DK void mul_cols(LP L, int lane, const float (*Mc)[NV], const float* x, int Y) {
     float y[NC];
@@ -3714,7 +3729,9 @@ struct TPhys {
     STAGE_MARK(ST_MAKE_ROWS);
     {
       float Mc[NC][NV];
-      load_cols(L, lane, Mc, false);
+      load_cols(L, lane, Mc);
+      // (the first pass's columns consumed and a sync's clobber between: else one of the two passes folds away)
+      STAGE_AGAIN(9, launder(Mc); TSYNC(); load_cols(L, lane, Mc));
       STAGE_MARK(ST_LOAD_COLS);
       smooth_acc(L, lane, Mc);
       STAGE_AGAIN(4, smooth_acc(L, lane, Mc));
@@ -3816,7 +3833,7 @@ struct TPhys {
     LAT_T(11, s);
     {
       float Mc[NC][NV];
-      load_cols(L, lane, Mc, false);
+      load_cols(L, lane, Mc);
       LAT_T(12, s);
       float SL[6], SR[6], cwp;
       warm_start_a0(L, lane, Mc, SL, SR);
@@ -3868,7 +3885,7 @@ struct TPhys {
     ev_wait(EV_M, s + 1);
     LAT_T(30, s);
     float Mc[NC][NV];
-    load_cols(L, lane, Mc, false);
+    load_cols(L, lane, Mc);
     Fac F;
     smooth_factor(F, lane, Mc);
     LAT_T(31, s);
@@ -3921,7 +3938,7 @@ struct TPhys {
     ev_wait(EV_M, s + 1);
     LAT2_T(6, s);
     float Mc[NC][NV];
-    load_cols(L, lane, Mc, false);
+    load_cols(L, lane, Mc);
     ev_wait(EV_WA, s + 1);
     LAT2_T(7, s);
     const bool ok = newton_fused<false, TL::XDIR>(L, lane, Mc);
@@ -3939,7 +3956,7 @@ struct TPhys {
     LAT2_T(11, s);
     {
       float Mc[NC][NV];
-      load_cols(L, lane, Mc, false);
+      load_cols(L, lane, Mc);
       LAT2_T(12, s);
       float SL[6], SR[6], cwp;
       warm_start_a0(L, lane, Mc, SL, SR);

@@ -49,7 +49,8 @@ def composed_rough_scene(tmpdir: str) -> str:
 
 
 # Edited scenes for tests (tests/golden/models/): what a user of the reference does when they change
-# the MJCF. Each is (robot-XML substitutions, scene-XML substitutions); the model compiler and
+# the MJCF. Each is (robot-XML substitutions, scene-XML substitutions), a substitution being a pair of
+# strings or a function of the text; the model compiler and
 # native.model_library turn them into kernels with no hand edits (codegen.py).
 SLOPE_MU = 0.2                        # floor friction of the slope scenes
 SLOPE_STICK, SLOPE_SLIDE = 0.15, 0.40  # tan(slope) below / above the friction angle atan(0.2)
@@ -63,6 +64,26 @@ def _slope(tan_theta: float) -> str:
 
 
 _INC = '<include file="open_duck_mini_v2.xml"/>'
+
+
+def _head_last_robot(robot: str) -> str:
+    """the neck's body moves behind the right leg's among the trunk's children: the same robot with
+    another dof order (free joint, left leg 6-10, right leg 11-15, head 16-19) and so another dof tree"""
+    i = robot.index("        <!-- Link neck_pitch_assembly -->")
+    j = robot.index("        <!-- Link hip_roll_assembly_2 -->")
+    k = robot.index("      </body>\n    </body>\n  </worldbody>")
+    assert i < j < k
+    return robot[:i] + robot[j:k] + robot[i:j] + robot[k:]
+
+
+def _head_last_scene(scene: str) -> str:
+    """the home key's qpos in the new joint order (ctrl keeps the actuators' order)"""
+    m = re.search(r'qpos="([^"]*)"', scene)
+    q = m.group(1).split()
+    assert len(q) == 21
+    return scene[:m.start(1)] + " ".join(q[:12] + q[16:] + q[12:16]) + scene[m.end(1):]
+
+
 EDITED = {
     # a stiffer servo, an 8 % larger collision foot and a grippier floor
     "flat_terrain_edited": ([('<position kp="13.37"', '<position kp="16.0"'),
@@ -74,20 +95,28 @@ EDITED = {
     # no joint damping, no dof friction, no servo: a conservative articulated body in flight
     "flat_terrain_conservative": ([('damping="0.56" frictionloss="0.068"', 'damping="0" frictionloss="0"'),
                                    ('<position kp="13.37"', '<position kp="0"')], []),
+    # the head limb after both legs: dof_parentid differs from every shipped scene's (NV stays 20)
+    "flat_terrain_head_last": ([_head_last_robot], [_head_last_scene]),
 }
+
+
+def _apply(text: str, edits) -> str:
+    for e in edits:
+        if callable(e):
+            text = e(text)
+        else:
+            assert e[0] in text, e[0]
+            text = text.replace(e[0], e[1])
+    return text
 
 
 def edited_scene(tmpdir: str, robot_edits, scene_edits) -> str:
     xmls = os.path.join(REF, "xmls")
     robot = open(os.path.join(xmls, "open_duck_mini_v2.xml")).read()
-    for a, b in robot_edits:
-        assert a in robot, a
-        robot = robot.replace(a, b)
+    robot = _apply(robot, robot_edits)
     robot = robot.replace('meshdir="assets"', f'meshdir="{xmls}/assets"')
     scene = open(os.path.join(xmls, "scene_flat_terrain.xml")).read()
-    for a, b in scene_edits:
-        assert a in scene, a
-        scene = scene.replace(a, b)
+    scene = _apply(scene, scene_edits)
     with open(os.path.join(tmpdir, "open_duck_mini_v2.xml"), "w") as f:
         f.write(robot)
     path = os.path.join(tmpdir, "scene.xml")
