@@ -3,7 +3,7 @@
  *
  * The reference decides whether an exported policy goes on the robot by running it in its deployment
  * control loop (playground/open_duck_mini_v2/mujoco_infer.py:156-241 on mujoco_infer_base.py), which is
- * not the training env: +1.3 on the accelerometer's x, a motor-speed limit, no action delay, noise or
+ * not the training env: +1.3 on the accelerometer's x, a motor-speed limit, no latency, noise or
  * pushes. One control period of that loop for N robots is four launches on one stream:
  *
  *   duck_physics_step   mj_step x decimation (mujoco_infer.py:170-174), 10 substeps, with `aux`
@@ -15,7 +15,11 @@
  *
  * and, only when the caller disturbs the loop as the training env does (noise, changing commands, pushes),
  * duck_fleet_disturb between duck_fleet_observe and duck_policy_act; and, only when the caller keeps a flight
- * recorder, duck_fleet_record after duck_fleet_actuate.
+ * recorder, duck_fleet_record after duck_fleet_actuate; and, only when the caller configures a latency,
+ * duck_fleet_actuate_delayed in duck_fleet_actuate's place and, when an IMU delay is among it,
+ * duck_fleet_sense_delay right after duck_fleet_observe. A period's order, optional launches in brackets:
+ *
+ *   physics, observe, [sense_delay], [disturb], policy, actuate or actuate_delayed, [record]
  *
  * The entries are model-agnostic: a host descriptor filled from the compiled model tells them where
  * the sensors, the actuated joints and the foot contacts are. Conventions are duck.h's: DEVICE
@@ -189,6 +193,61 @@ int duck_fleet_disturb(const duck_fleet_desc* desc, const duck_fleet_disturbance
 int duck_fleet_record(const duck_fleet_desc* desc, int N, int depth, int post, const float* qpos, const float* qvel,
                       const float* warm, const float* aux, const float* ctl, const float* obs, const float* action,
                       const float* alive, int32_t* head, int32_t* after, float* ring, void* stream);
+
+/* Latency of the deployment loop: the action that reaches the motors and the IMU sample that reaches the policy
+ * are each 0 to DUCK_FLEET_MAX_DELAY control periods old (the training env's action delay, joystick.py:361-376,
+ * and IMU delay, joystick.py:521-530). A delay is a whole number of periods (20 ms each);
+ * DUCK_FLEET_MAX_DELAY is the depth of the action history the control record already holds. A loop that
+ * configures no latency enqueues neither entry.
+ *
+ * lat [N][DUCK_FLEET_LAT_SIZE] row-major int32 = {act_lo, act_hi, sense_lo, sense_hi}, 0 <= lo <= hi <=
+ * DUCK_FLEET_MAX_DELAY, validated by the caller; the kernels clamp lo into [0, MAX_DELAY] and hi into
+ * [lo, MAX_DELAY], so that a bad row cannot address outside the robot's history or line. lo == hi is a fixed
+ * delay; otherwise the delay is drawn per robot and period, uniformly over lo..hi, both ends included. (The
+ * training env's randint(min, max) excludes max: its default action_min_delay = 0, action_max_delay = 3 is
+ * (0, 2) here.)
+ *
+ * The period's count lives on the device, for duck_fleet_disturb's reason: lat_tick [N] int32, p = lat_tick[e]
+ * the periods robot e completed since the latency was configured (0 then, set by the caller). It has one
+ * writer, duck_fleet_actuate_delayed, as its last store; duck_fleet_sense_delay, earlier in the period, reads
+ * the same p. A negative lat_tick is read as p = 0.
+ *
+ * Random stream, threefry2x32 (20 rounds), apart from the disturbances': key = derive_key(seed, robot_offset + e,
+ * DUCK_FLEET_LAT_TAG) (duck_fleet_disturb's key with the other tag; the latency has its own seed). Block 0 of
+ * period p is threefry2x32(key, (p, 0)); word 0 draws the action delay, word 1 the sensor delay:
+ *   d = lo + (((word >> 9) * (uint32_t)(hi - lo + 1)) >> 23)
+ * in integers: exact, and never above hi. A robot's draws depend on (seed, id, p) only -- not on N, the launch
+ * geometry or graph replay.
+ *
+ * duck_fleet_sense_delay, after duck_fleet_observe and before duck_fleet_disturb; enqueued only when some robot
+ * has sense_hi > 0. line [N][DUCK_FLEET_MAX_DELAY + 1][6] row-major float32 is the robot's delay line of obs
+ * columns 0-5 as duck_fleet_observe wrote them (gyro, then the accelerometer with the x offset; no noise yet).
+ * For robot e: the six words go to slot p % 3; then, with d the drawn sensor delay and d_eff = min(d, min(p, 2))
+ * (a line that is not yet full holds its oldest sample), when d_eff > 0 the six obs columns are overwritten
+ * with the words of slot (p - d_eff) % 3; when d_eff == 0 obs is not written. Words are copied as uint32_t:
+ * NaN payloads and -0 keep their bits. The noise of duck_fleet_disturb is added after the delay: it is i.i.d.
+ * per period, so the sum has the distribution of the training env's noise-then-history order, and the line
+ * stays a function of the true sensors. duck_fleet_observe's bookkeeping has run on the true sensors. Only the
+ * IMU columns are delayed; joint-encoder latency is not modelled. lat_tick is not written. desc gives nu.
+ *
+ * duck_fleet_actuate_delayed, in duck_fleet_actuate's place. The history shift is duck_fleet_actuate's:
+ * last_action etc. hold the policy's undelayed actions (state.info["last_act"] in training). After the shift,
+ * the action that forms the motor targets is history entry d, the drawn action delay: entry 0 this period's
+ * action, entry 1 last_last_action, entry 2 last_last_last_action. The history starts at zero actions, as the
+ * reference loop's and the training env's do, so a young history is not clamped. motor_targets, the
+ * speed-limit clip, prev_motor_targets and ctrl are duck_fleet_actuate's fp32 expressions in its order on that
+ * action: with d == 0 the result is duck_fleet_actuate's bit for bit. Last, lat_tick[e] = lat_tick[e] + 1.
+ *
+ * N == 0 launches nothing. */
+#define DUCK_FLEET_MAX_DELAY 2
+#define DUCK_FLEET_LAT_SIZE 4
+#define DUCK_FLEET_LAT_TAG 0x1A7Eu
+
+int duck_fleet_sense_delay(const duck_fleet_desc* desc, int N, uint64_t seed, int64_t robot_offset,
+                           const int32_t* lat_tick, const int32_t* lat, float* line, float* obs, void* stream);
+int duck_fleet_actuate_delayed(const duck_fleet_desc* desc, int N, uint64_t seed, int64_t robot_offset,
+                               int32_t* lat_tick, const int32_t* lat, const float* action, float* ctl,
+                               float* ctrl, void* stream);
 
 #ifdef __cplusplus
 }

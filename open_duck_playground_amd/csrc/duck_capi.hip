@@ -351,6 +351,83 @@ __global__ __launch_bounds__(FLEET_TPB) void fleet_record_kernel(
   }
 }
 
+// The loop's latency (include/duck_fleet.h: duck_fleet_sense_delay, duck_fleet_actuate_delayed), the same
+// 16-lane group per robot. Every lane of a group loads the robot's counter and its row of the table (broadcast
+// loads) and evaluates the one threefry block itself when the row asks for a draw, so the delay is a value of
+// the whole group with no LDS and no votes. A bad row is clamped: lo into [0, MAX_DELAY], hi into [lo, MAX_DELAY].
+__device__ __forceinline__ int fleet_delay(const int* __restrict__ row, int which, unsigned long long seed,
+                                           long long id, uint32_t p) {
+  int lo = row[2 * which], hi = row[2 * which + 1];
+  lo = lo < 0 ? 0 : (lo > DUCK_FLEET_MAX_DELAY ? DUCK_FLEET_MAX_DELAY : lo);
+  hi = hi < lo ? lo : (hi > DUCK_FLEET_MAX_DELAY ? DUCK_FLEET_MAX_DELAY : hi);
+  if (hi == lo) return lo;
+  uint32_t k0, k1, w0, w1;
+  derive_key(seed, id, DUCK_FLEET_LAT_TAG, k0, k1);
+  threefry2x32(k0, k1, p, 0u, w0, w1);
+  return lo + (int)((((which ? w1 : w0) >> 9) * (uint32_t)(hi - lo + 1)) >> 23);
+}
+
+// Lanes 0-5 carry the six IMU words: into the line's slot p % 3, then, when the delay reaches back, out of the
+// slot an earlier period's launch wrote. lat_tick is read only.
+__global__ __launch_bounds__(FLEET_TPB) void fleet_sense_delay_kernel(int nu, int n, unsigned long long seed,
+                                                                      long long robot_offset,
+                                                                      const int* __restrict__ lat_tick,
+                                                                      const int* __restrict__ lat, uint32_t* line,
+                                                                      uint32_t* obs) {
+  const int lane = threadIdx.x % FLEET_TEAM;
+  const int e0 = blockIdx.x * (FLEET_TPB / FLEET_TEAM) + threadIdx.x / FLEET_TEAM;
+  if (e0 >= n || lane >= 6) return;
+  const size_t e = e0;
+  const int p0 = lat_tick[e];
+  const uint32_t p = p0 < 0 ? 0u : (uint32_t)p0;
+  const int d = fleet_delay(lat + e * DUCK_FLEET_LAT_SIZE, 1, seed, robot_offset + (long long)e, p);
+  const uint32_t fill = p < (uint32_t)DUCK_FLEET_MAX_DELAY ? p : (uint32_t)DUCK_FLEET_MAX_DELAY;
+  const uint32_t d_eff = (uint32_t)d < fill ? (uint32_t)d : fill;
+  constexpr uint32_t SLOTS = DUCK_FLEET_MAX_DELAY + 1;
+  uint32_t* o = obs + e * DUCK_FLEET_OBS_SIZE(nu) + lane;
+  uint32_t* l = line + e * (SLOTS * 6) + lane;
+  l[(p % SLOTS) * 6] = *o;
+  if (d_eff > 0) *o = l[((p - d_eff) % SLOTS) * 6];
+}
+
+// fleet_actuate_kernel on history entry d. Every lane has read the counter (one load of the whole wave) before
+// lane 0's store, which depends on it, can issue; it is the kernel's last store.
+__global__ __launch_bounds__(FLEET_TPB) void fleet_actuate_delayed_kernel(const duck_fleet_desc D, int n,
+                                                                          unsigned long long seed,
+                                                                          long long robot_offset, int* lat_tick,
+                                                                          const int* __restrict__ lat,
+                                                                          const float* __restrict__ action,
+                                                                          float* ctl, float* __restrict__ ctrl) {
+#pragma clang fp contract(off)
+  const int a = threadIdx.x % FLEET_TEAM;
+  const int e0 = blockIdx.x * (FLEET_TPB / FLEET_TEAM) + threadIdx.x / FLEET_TEAM;
+  const int nu = D.nu;
+  if (e0 >= n) return;
+  const size_t e = e0;
+  const int p0 = lat_tick[e];
+  if (a >= nu) return;
+  const int d = fleet_delay(lat + e * DUCK_FLEET_LAT_SIZE, 0, seed, robot_offset + (long long)e,
+                            p0 < 0 ? 0u : (uint32_t)p0);
+  float* c = ctl + e * DUCK_FLEET_CTL_SIZE(nu);
+  const float act = action[e * nu + a], last = c[a], last_last = c[nu + a];
+  c[2 * nu + a] = last_last;
+  c[nu + a] = last;
+  c[a] = act;
+  const float used = d == 0 ? act : (d == 1 ? last : last_last);  // entry d of the shifted history
+  const float scaled = used * D.action_scale;
+  float mt = D.act_default[a] + scaled;
+  if (D.speed_limits) {
+    const float prev = c[4 * nu + a];
+    const float lo = prev - D.target_step, hi = prev + D.target_step;
+    mt = mt < lo ? lo : mt;  // np.clip: a NaN target stays NaN
+    mt = mt > hi ? hi : mt;
+    c[4 * nu + a] = mt;
+  }
+  c[3 * nu + a] = mt;
+  ctrl[(size_t)a * n + e] = mt;
+  if (a == 0) lat_tick[e] = (int)((uint32_t)p0 + 1u);
+}
+
 static const char* fleet_desc_error(const duck_fleet_desc* d) {
   if (d->nq < 1 || d->nv < 1 || d->nu < 1 || d->nu > DUCK_FLEET_MAX_NU) return "nq, nv >= 1 and 1 <= nu <= 16";
   for (int a = 0; a < d->nu; a++)
@@ -458,6 +535,38 @@ int duck_fleet_record(const duck_fleet_desc* d, int n, int depth, int post, cons
                      depth, post, (const uint32_t*)qpos, (const uint32_t*)qvel, (const uint32_t*)warm,
                      (const uint32_t*)aux, (const uint32_t*)ctl, (const uint32_t*)obs, (const uint32_t*)action, alive,
                      head, after, (uint32_t*)ring);
+  HIPCHECK(hipGetLastError());
+  return DUCK_OK;
+}
+
+int duck_fleet_sense_delay(const duck_fleet_desc* d, int n, uint64_t seed, int64_t robot_offset, const int32_t* lat_tick,
+                           const int32_t* lat, float* line, float* obs, void* stream) {
+  g_err.clear();
+  if (!d || !lat_tick || !lat || !line || !obs) return duck_fail(DUCK_EINVAL, "duck_fleet_sense_delay: null pointer");
+  if (n < 0 || n > (1 << 27)) return duck_fail(DUCK_EINVAL, "duck_fleet_sense_delay: bad size (0 <= N <= 2^27)");
+  if (const char* why = fleet_desc_error(d))
+    return duck_fail(DUCK_EINVAL, std::string("duck_fleet_sense_delay: ") + why);
+  if (n == 0) return DUCK_OK;
+  const int per = FLEET_TPB / FLEET_TEAM;
+  hipLaunchKernelGGL(fleet_sense_delay_kernel, dim3((n + per - 1) / per), dim3(FLEET_TPB), 0, (hipStream_t)stream,
+                     d->nu, n, (unsigned long long)seed, (long long)robot_offset, lat_tick, lat, (uint32_t*)line,
+                     (uint32_t*)obs);
+  HIPCHECK(hipGetLastError());
+  return DUCK_OK;
+}
+
+int duck_fleet_actuate_delayed(const duck_fleet_desc* d, int n, uint64_t seed, int64_t robot_offset, int32_t* lat_tick,
+                               const int32_t* lat, const float* action, float* ctl, float* ctrl, void* stream) {
+  g_err.clear();
+  if (!d || !lat_tick || !lat || !action || !ctl || !ctrl)
+    return duck_fail(DUCK_EINVAL, "duck_fleet_actuate_delayed: null pointer");
+  if (n < 0 || n > (1 << 27)) return duck_fail(DUCK_EINVAL, "duck_fleet_actuate_delayed: bad size (0 <= N <= 2^27)");
+  if (const char* why = fleet_desc_error(d))
+    return duck_fail(DUCK_EINVAL, std::string("duck_fleet_actuate_delayed: ") + why);
+  if (n == 0) return DUCK_OK;
+  const int per = FLEET_TPB / FLEET_TEAM;
+  hipLaunchKernelGGL(fleet_actuate_delayed_kernel, dim3((n + per - 1) / per), dim3(FLEET_TPB), 0, (hipStream_t)stream,
+                     *d, n, (unsigned long long)seed, (long long)robot_offset, lat_tick, lat, action, ctl, ctrl);
   HIPCHECK(hipGetLastError());
   return DUCK_OK;
 }

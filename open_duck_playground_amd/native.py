@@ -27,6 +27,9 @@ DuckFleetDesc = HEADERS.structs["duck_fleet_desc"]
 DuckFleetDisturbance = HEADERS.structs["duck_fleet_disturbance"]
 FLEET_MAX_NU = HEADERS.consts["DUCK_FLEET_MAX_NU"]
 FLEET_PUSH_SIZE = HEADERS.consts["DUCK_FLEET_PUSH_SIZE"]
+FLEET_MAX_DELAY = HEADERS.consts["DUCK_FLEET_MAX_DELAY"]
+FLEET_LAT_SIZE = HEADERS.consts["DUCK_FLEET_LAT_SIZE"]
+FLEET_LAT_TAG = HEADERS.consts["DUCK_FLEET_LAT_TAG"]
 EXPORTS = list(HEADERS.funcs)
 
 

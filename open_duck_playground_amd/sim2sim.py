@@ -19,7 +19,8 @@ randomised models -- takes thousands of runs. ``python -m open_duck_playground_a
 reference's flags and adds ``--num_robots``, ``--periods``, ``--command_grid``, ``--randomize``, ``--out``, and the
 disturbances the training env has and the reference's deployment loop lacks: ``--push_grid``, ``--push_at``,
 ``--push_every``, ``--push_magnitude``, ``--recovery_window``, ``--noise``, ``--noise_seed``,
-``--resample_commands``; and the flight recorder, ``--record_falls``, ``--record_post``, ``--record_out``,
+``--resample_commands``; the latency the training env randomises, ``--delay_grid``, ``--delay_jitter``,
+``--delay_seed``; and the flight recorder, ``--record_falls``, ``--record_post``, ``--record_out``,
 ``--record_max``: the last periods of every robot that fell, written to an ``.npz`` (the reference keeps what
 its loop saw in ``saved_obs``; the file holds the same observations and the state around them).
 """
@@ -277,6 +278,15 @@ class FleetInfer:
     With none configured the loop is the four launches above, unchanged. ``robot_offset`` is the global id of
     robot 0 in the disturbance stream (a robot's draws depend on the seed, its global id and the period only).
 
+    Latency (off by default; ``set_latency(action, sense, seed)`` or ``latency=(action, sense, seed)``): the
+    action that reaches the motors and the IMU sample that reaches the policy are 0 to 2 control periods old,
+    fixed per robot or drawn per robot and period (the training env's action and IMU delay). With a latency
+    set, duck_fleet_actuate_delayed takes duck_fleet_actuate's place (no launch more), and with an IMU delay
+    among it duck_fleet_sense_delay runs right after duck_fleet_observe (one launch more): physics -> observe ->
+    [sense_delay] -> [disturb] -> policy -> actuate or actuate_delayed -> [record]. The latency has its own
+    seed and its own period count ``lat_tick`` on the device. With none set (``latent()`` False) the loop
+    enqueues exactly the launches above.
+
     The flight recorder (off by default; ``set_recorder(depth, post)`` or ``recorder=(depth, post)``): one more
     launch at the end of the period, duck_fleet_record, keeps every robot's last ``depth`` periods in a ring on
     the device -- the state the next period starts from, the control record, the observation the policy saw,
@@ -285,13 +295,15 @@ class FleetInfer:
     ``recorded(robot)`` returns the frames in period order; ``replay(robot, frame)`` returns a one-robot fleet
     loaded from a recorded frame, whose next periods reproduce the robot's bit for bit."""
 
-    CHUNK = 50   # control periods per captured graph (200 launches; 250 with disturbances; 50 more with a recorder)
+    # control periods per captured graph (200 launches; 50 more with disturbances, 50 more with an IMU delay, 50 more
+    # with a recorder: 400 at the most)
+    CHUNK = 50
 
     def __init__(self, model_path: str = "flat_terrain", onnx_model_path: Optional[str] = None, num_robots: int = 1,
                  reference_data: Optional[str] = None, standing: bool = False, device="cuda:0",
                  randomize: Optional[int] = None, command_schedule: Optional[tuple] = None,
                  pushes: Optional[tuple] = None, noise: Optional[tuple] = None, recorder: Optional[tuple] = None,
-                 robot_offset: int = 0):
+                 robot_offset: int = 0, latency: Optional[tuple] = None):
         import ctypes as C
 
         from .native import DuckError, check
@@ -354,6 +366,10 @@ class FleetInfer:
         self.dis = DuckFleetDisturbance()
         self.sched = self.sched_id = self.push = None
         self.robot_offset = int(robot_offset)
+        # the latency (include/duck_fleet.h duck_fleet_sense_delay, duck_fleet_actuate_delayed): off
+        self.lat = self.lat_tick = self.line = None
+        self.lat_seed = self.lat_base = 0
+        self.lat_sense = False
         # the flight recorder (include/duck_fleet.h duck_fleet_record): off
         self.frame_fields = frame_fields(int(m.nq), int(m.nv), nu)
         self.ring = self.rec_head = self.rec_after = None
@@ -369,12 +385,15 @@ class FleetInfer:
             self.set_noise(*noise)
         if recorder is not None:
             self.set_recorder(*recorder)
+        if latency is not None:
+            self.set_latency(*latency)
 
     def restart(self) -> None:
         """Every robot back to the loop's start, with the randomisation record ``dr`` as it is now.
         MJInferBase.__init__: MjData at qpos0 with zero ctrl, one mj_step, then the home keyframe's qpos and
         ctrl (the velocity of that first step is kept); mujoco_infer.py:49-60 for the control record. The
-        period count goes back to 0, a command schedule to its segment 0, and a recorder to no frames."""
+        period count goes back to 0, a command schedule to its segment 0, a recorder to no frames and a latency
+        to its first period (the delay line fills anew)."""
         m, n = self.model, self.num_robots
         col = lambda a: torch.tensor(np.asarray(a, dtype=np.float32)[:, None], device=self.device)  # noqa: E731
         key = m.names["key"].index("home")
@@ -395,6 +414,9 @@ class FleetInfer:
         if self.ring is not None:
             self.rec_head.zero_()
             self.rec_after.zero_()
+        self.lat_base = 0
+        if self.lat_tick is not None:
+            self.lat_tick.zero_()
 
     # --- launches -----------------------------------------------------------------------------
     def _stream(self):
@@ -417,15 +439,47 @@ class FleetInfer:
                                          self.obs.data_ptr(), self.acc.data_ptr(), self.alive.data_ptr(),
                                          self._stream()), L)
 
-    def act(self):
-        """duck_policy_act on ``obs``, then duck_fleet_actuate: history, motor targets, ctrl."""
-        import ctypes as C
+    def policy(self):
+        """duck_policy_act on ``obs``."""
         from .native import lib
-        L, P = self._lib, lib()   # the policy kernel ships with libduck.so only, the rest with the model's library
+        P = lib()   # the policy kernel ships with libduck.so only, the rest with the model's library
         self._check(P.duck_policy_act(self.num_robots, *self._policy_args, self.obs.data_ptr(), None,
                                       self.action.data_ptr(), self._stream()), P)
+
+    def actuate(self):
+        """duck_fleet_actuate: history, motor targets, ctrl."""
+        import ctypes as C
+        L = self._lib
         self._check(L.duck_fleet_actuate(C.byref(self.desc), self.num_robots, self.action.data_ptr(),
                                          self.ctl.data_ptr(), self.ctrl.data_ptr(), self._stream()), L)
+
+    def act(self):
+        """duck_policy_act on ``obs``, then duck_fleet_actuate, or with a latency duck_fleet_actuate_delayed."""
+        self.policy()
+        if self.latent():
+            self.actuate_delayed()
+        else:
+            self.actuate()
+
+    def latent(self) -> bool:
+        """Whether a latency is set (duck_fleet_actuate_delayed in duck_fleet_actuate's place)."""
+        return self.lat is not None
+
+    def sense_delay(self):
+        """duck_fleet_sense_delay on this period's ``obs``: the IMU columns into the delay line and, delayed, back."""
+        import ctypes as C
+        L = self._lib
+        self._check(L.duck_fleet_sense_delay(C.byref(self.desc), self.num_robots, self.lat_seed, self.robot_offset,
+                                             self.lat_tick.data_ptr(), self.lat.data_ptr(), self.line.data_ptr(),
+                                             self.obs.data_ptr(), self._stream()), L)
+
+    def actuate_delayed(self):
+        """duck_fleet_actuate_delayed: duck_fleet_actuate on the delayed entry of the history, then lat_tick."""
+        import ctypes as C
+        L = self._lib
+        self._check(L.duck_fleet_actuate_delayed(C.byref(self.desc), self.num_robots, self.lat_seed, self.robot_offset,
+                                                 self.lat_tick.data_ptr(), self.lat.data_ptr(), self.action.data_ptr(),
+                                                 self.ctl.data_ptr(), self.ctrl.data_ptr(), self._stream()), L)
 
     def disturbed(self) -> bool:
         """Whether a schedule, a push table or a non-zero noise is set (the loop's fifth launch)."""
@@ -453,9 +507,12 @@ class FleetInfer:
 
     def _periods(self, k: int, rec: Optional[torch.Tensor] = None, t0: int = 0):
         disturbed, recording = self.disturbed(), self.ring is not None
+        sense = self.latent() and self.lat_sense
         for t in range(k):
             self._physics(self.decimation)
             self.observe()
+            if sense:
+                self.sense_delay()
             if disturbed:
                 self.disturb()
             if rec is not None:
@@ -599,8 +656,8 @@ class FleetInfer:
         per robot and period from the stream of ``seed`` (which also draws the random pushes). ``scales``
         [obs_size] defaults to ``default_noise_scales()``. The training env adds the noise to the raw joint
         velocity and scales by dof_vel_scale afterwards; here it is added to the scaled column, with the scale
-        multiplied in. duck_fleet_observe's bookkeeping has run on the true sensors; action and IMU delay
-        are not modelled. ``level=0`` turns the noise off."""
+        multiplied in. duck_fleet_observe's bookkeeping has run on the true sensors. The noise is added after an
+        IMU delay (``set_latency``). ``level=0`` turns the noise off."""
         from .native import DuckError
         sc = self.default_noise_scales() if scales is None else np.asarray(scales, dtype=np.float64)
         if sc.shape != (self.obs_size,):
@@ -615,6 +672,58 @@ class FleetInfer:
         self.dis.seed = seed
         for k in range(self.obs_size):
             self.dis.noise_scale[k] = float(eff[k])
+
+    # --- latency (include/duck_fleet.h duck_fleet_sense_delay, duck_fleet_actuate_delayed) ----------------
+    def set_latency(self, action=0, sense=0, seed: int = 0) -> None:
+        """Latency in whole control periods (20 ms each): ``action`` delays the action that forms the motor targets
+        (the training env's action delay, joystick.py:361-376), ``sense`` the gyro and accelerometer columns of the
+        observation (its IMU delay, joystick.py:521-530). Each is a scalar, an [N] list or array of integers, or a
+        tuple ``(lo, hi)`` of such: drawn per robot and period, uniformly over lo..hi with both ends included, from
+        the stream of ``seed`` (the latency's own; the training env's randint excludes its upper end: its default
+        0..3 is ``(0, 2)`` here). Values lie in [0, 2]. The action history the policy sees stays undelayed, the
+        bookkeeping runs on the true sensors, the noise is added after the delay; the joint encoders are not
+        delayed. ``set_latency(None)``, or all zeros, turns the latency off. A latency starts anew when set: its
+        period count ``lat_tick`` at 0, the delay line empty (``lat_base`` = the periods run since ``restart()``)."""
+        from .native import FLEET_LAT_SIZE, FLEET_MAX_DELAY, DuckError
+        n = self.num_robots
+        self.graph = None
+        rows = np.zeros((n, FLEET_LAT_SIZE), dtype=np.int32)
+        if action is not None:
+            for k, (name, v) in enumerate((("action", action), ("sense", sense))):
+                if isinstance(v, tuple) and len(v) != 2:
+                    raise DuckError(f"{name} as a tuple is (lo, hi), got {len(v)} values")
+                for j, (end, w) in enumerate(zip(("lo", "hi"), v if isinstance(v, tuple) else (v, v))):
+                    try:
+                        a = np.asarray(w, dtype=np.float64)
+                    except (TypeError, ValueError):
+                        raise DuckError(f"{name} must be integers, got {w!r}") from None
+                    if a.shape not in ((), (n,)):
+                        raise DuckError(f"{name} must be a scalar or [{n}], got {tuple(a.shape)}")
+                    if not np.isfinite(a).all() or (a != np.floor(a)).any():
+                        raise DuckError(f"{name} must be integers (whole control periods)")
+                    if (a < 0).any() or (a > FLEET_MAX_DELAY).any():
+                        raise DuckError(f"{name} must lie in [0, {FLEET_MAX_DELAY}] control periods")
+                    rows[:, 2 * k + j] = a
+                if (rows[:, 2 * k] > rows[:, 2 * k + 1]).any():
+                    raise DuckError(f"{name} as (lo, hi) needs lo <= hi")
+        if int(seed) != seed:
+            raise DuckError(f"the latency seed must be an integer, got {seed!r}")
+        if not rows.any():
+            self.lat = self.lat_tick = self.line = None
+            self.lat_seed, self.lat_sense = 0, False
+            return
+        self._load_latency(rows, seed)
+
+    def _load_latency(self, rows: np.ndarray, seed: int) -> None:
+        """The latency table ``rows`` [N][4] as it is (all zeros included): new buffers, the count at 0."""
+        from .native import FLEET_MAX_DELAY
+        n = self.num_robots
+        self.graph = None
+        self.lat = torch.as_tensor(np.ascontiguousarray(rows, dtype=np.int32)).to(self.device)
+        self.lat_tick = torch.zeros(n, dtype=torch.int32, device=self.device)
+        self.line = torch.zeros(n, FLEET_MAX_DELAY + 1, 6, dtype=torch.float32, device=self.device)
+        self.lat_seed, self.lat_base = int(seed) & 0xFFFFFFFFFFFFFFFF, self.periods_done
+        self.lat_sense = bool((np.asarray(rows)[:, 3] > 0).any())
 
     # --- the flight recorder (include/duck_fleet.h duck_fleet_record) ----------------------------------
     def set_recorder(self, depth: Optional[int], post: int = 0) -> None:
@@ -660,7 +769,9 @@ class FleetInfer:
     def replay(self, robot: int, frame: int = 0) -> "FleetInfer":
         """A one-robot fleet that continues robot ``robot`` from its recorded frame ``frame`` (an index into
         ``recorded(robot)``; negative from the newest): the same model, policy, ``standing`` flag and noise,
-        the robot's randomisation record, schedule and push row, and its global id in the disturbance stream.
+        the robot's randomisation record, schedule, push row and latency row, and its global id in the disturbance
+        and latency streams. With an IMU delay the delay line is rebuilt from the raw sensors of the frame and of
+        the one before it; a robot whose IMU delay reaches 2 cannot be replayed from the oldest frame it holds.
         The loop is a pure function of what a frame holds, that record and that stream, so running the replay
         k periods reproduces the k periods the robot ran after that frame, bit for bit. The fleet's settings
         are taken as they are now: they must not have changed since the frame was written."""
@@ -688,6 +799,29 @@ class FleetInfer:
         r.ctrl[:, 0].copy_(r.ctl_field("motor_targets")[0])
         if self.disturbed():   # the device's period count at that frame: it has advanced once per period since
             r.tick.copy_(self.tick[robot:robot + 1] - (self.periods_done - p))
+        if self.latent():
+            row = self.lat[robot:robot + 1].cpu().numpy()
+            r._load_latency(row, self.lat_seed)
+            after = int(self.lat_tick[robot]) - (self.periods_done - p)   # lat_tick once the frame's period was done
+            if after < 0:
+                raise DuckError(f"frame {frame!r} of robot {robot} was written before the latency was set")
+            r.lat_tick.fill_(after)
+            r.lat_base = p - after
+            q = after - 1                     # ... and in the period that wrote the frame
+            o, _ = self.frame_fields["sensors"]
+            k = int(frame) % len(frames)
+
+            def sample(fr):   # obs columns 0-5 as duck_fleet_observe wrote them, from a frame's raw sensors
+                w = np.array(fr[o:o + 6], dtype=np.float32)
+                w[3] = w[3] + np.float32(self.desc.accel_x_offset)
+                return torch.tensor(w, device=self.device)
+            if q >= 0:
+                r.line[0, q % 3].copy_(sample(frames[k]))
+            if q >= 1 and int(row[0, 3]) == 2:
+                if k == 0:
+                    raise DuckError(f"robot {robot}'s IMU delay reaches 2 periods back and the frame before frame "
+                                    f"{frame!r} is not held: replay from a later frame")
+                r.line[0, (q - 1) % 3].copy_(sample(frames[k - 1]))
         r.periods_done = p
         return r
 
@@ -870,6 +1004,73 @@ def disturbance_plan(args, cells: np.ndarray):
     return plan
 
 
+PERIOD_MS = 20.0   # one control period: sim_dt * decimation = 0.002 s * 10
+
+
+def delay_grid(spec: str) -> np.ndarray:
+    """``NAxNS`` -> the [NA * NS][2] (action delay, sense delay) cells in control periods: a in range(NA), s in
+    range(NS), 1 <= NA, NS <= DUCK_FLEET_MAX_DELAY + 1."""
+    from .native import FLEET_MAX_DELAY
+    try:
+        na, ns = (int(v) for v in spec.lower().split("x"))
+        assert 1 <= min(na, ns) and max(na, ns) <= FLEET_MAX_DELAY + 1
+    except Exception:
+        raise ValueError(f"--delay_grid wants NAxNS with 1 <= NA, NS <= {FLEET_MAX_DELAY + 1}, got {spec!r}") from None
+    return np.array([(a, s) for a in range(na) for s in range(ns)], dtype=np.int32)
+
+
+def robot_delay_cells(num_robots: int, n_command: int, n_push: int, n_delay: int) -> np.ndarray:
+    """Round-robin over command cell x push cell x delay cell: ``robot_cells``' two, then delay cell
+    (r div (n_command * n_push)) mod n_delay."""
+    return (np.arange(num_robots) // (n_command * n_push)) % n_delay
+
+
+def latency_plan(args, n_command: int, n_push: int = 1):
+    """The command line's latency flags, or None without ``--delay_grid``: {"cells" [D][2], "cell" [N],
+    "latency": ``set_latency``'s arguments, "echo": the settings for the report}. With ``--delay_jitter`` a robot
+    draws per period from [0, its cell's value] instead of holding it."""
+    if args.delay_grid is None:
+        if args.delay_jitter:
+            raise ValueError("--delay_jitter needs --delay_grid NAxNS")
+        return None
+    cells = delay_grid(args.delay_grid)
+    cell = robot_delay_cells(args.num_robots, n_command, n_push, len(cells))
+    a, s = cells[cell, 0], cells[cell, 1]
+    zero = np.zeros_like(a)
+    latency = ((zero, a), (zero, s), args.delay_seed) if args.delay_jitter else (a, s, args.delay_seed)
+    echo = {"delay_grid": args.delay_grid, "delay_jitter": bool(args.delay_jitter), "delay_seed": args.delay_seed}
+    return {"cells": cells, "cell": cell, "latency": latency, "echo": echo}
+
+
+def latency_report(rep: Dict[str, np.ndarray], acc: np.ndarray, delay_cell: np.ndarray, cells: np.ndarray,
+                   n_periods: int, jitter: bool = False) -> list:
+    """Per delay cell (``delay_cell`` [N], each robot's cell): the delays in periods and ms (with ``jitter`` the
+    upper end of the drawn range), the count, the share that never fell, the mean periods survived and the rms
+    errors over the cell's surviving periods (``grid_report``'s aggregation of ``acc``)."""
+    cell = np.asarray(delay_cell)
+    out = []
+    for c in range(len(cells)):
+        m = cell == c
+        a = np.asarray(acc)[m].astype(np.float64)
+        tot = a.sum(0) if len(a) else np.zeros(6)
+        rms = (lambda v: float(np.sqrt(v / tot[0]))) if tot[0] > 0 else (lambda v: None)
+        da, ds = int(cells[c][0]), int(cells[c][1])
+        out.append({"cell": c, "action_delay": da, "sense_delay": ds, "action_delay_ms": da * PERIOD_MS,
+                    "sense_delay_ms": ds * PERIOD_MS, "jitter": bool(jitter), "count": int(len(a)),
+                    "survival_rate": float(np.mean(~np.asarray(rep["fell"], dtype=bool)[m])) if len(a) else None,
+                    "mean_periods": float(a[:, 0].mean()) if len(a) else None, "periods": int(n_periods),
+                    "rms_lin_err": rms(tot[4]), "rms_yaw_err": rms(tot[5])})
+    return out
+
+
+def add_latency_arguments(p) -> None:
+    p.add_argument("--delay_grid", type=str, default=None, metavar="NAxNS",
+                   help="action delays 0..NA-1 x IMU delays 0..NS-1 in control periods of 20 ms (NA, NS <= 3)")
+    p.add_argument("--delay_jitter", action="store_true", default=False,
+                   help="draw each robot's delays per period from [0, its cell's value] instead of holding them")
+    p.add_argument("--delay_seed", type=int, default=0, metavar="SEED")
+
+
 def add_recorder_arguments(p) -> None:
     p.add_argument("--record_falls", type=int, default=None, metavar="DEPTH",
                    help="keep every robot's last DEPTH periods on the device, frozen at its fall")
@@ -917,6 +1118,7 @@ def build_parser():
     p.add_argument("--out", type=str, default=None, metavar="report.json")
     p.add_argument("--device", type=str, default="cuda:0")
     add_disturbance_arguments(p)
+    add_latency_arguments(p)
     add_recorder_arguments(p)
     return p
 
@@ -937,6 +1139,8 @@ def main(argv=None) -> int:
     args = parse_arguments(argv)
     cells = command_grid(args.command_grid)
     plan = disturbance_plan(args, cells)
+    n_push = 1 if plan is None or plan["push_cells"] is None else len(plan["push_cells"])
+    delays = latency_plan(args, len(cells), n_push)
     fleet = FleetInfer(args.model_path, args.onnx_model_path, args.num_robots, reference_data=args.reference_data,
                        standing=args.standing, device=args.device, randomize=args.randomize)
     fleet.set_commands(cells[np.arange(args.num_robots) % len(cells)])
@@ -947,6 +1151,8 @@ def main(argv=None) -> int:
             fleet.set_pushes(*plan["pushes"])
         if args.noise:
             fleet.set_noise(args.noise, args.noise_seed)
+    if delays is not None:
+        fleet.set_latency(*delays["latency"])
     if args.record_falls is not None:
         fleet.set_recorder(args.record_falls, args.record_post)
     t0 = time.time()
@@ -964,6 +1170,10 @@ def main(argv=None) -> int:
                                         args.recovery_window)
             for row in doc["pushes"]:
                 row["magnitude"], row["theta"] = (float(v) for v in plan["push_cells"][row["cell"]])
+    if delays is not None:
+        doc["delay"] = delays["echo"]
+        doc["latency"] = latency_report(rep, fleet.acc.cpu().numpy(), delays["cell"], delays["cells"], args.periods,
+                                        args.delay_jitter)
     if args.record_falls is not None:
         written = 0
         if args.record_out:
