@@ -19,7 +19,9 @@
  * duck_fleet_actuate_delayed in duck_fleet_actuate's place and, when an IMU delay is among it,
  * duck_fleet_sense_delay right after duck_fleet_observe. A period's order, optional launches in brackets:
  *
- *   physics, observe, [sense_delay], [disturb], policy, actuate or actuate_delayed, [record]
+ *   physics, observe, [sense_delay], [disturb], policy or follow, actuate or actuate_delayed, [record]
+ *
+ * (duck_fleet_follow, in duck_policy_act's place, when the robots follow a recorded log instead of a policy.)
  *
  * The entries are model-agnostic: a host descriptor filled from the compiled model tells them where
  * the sensors, the actuated joints and the foot contacts are. Conventions are duck.h's: DEVICE
@@ -248,6 +250,38 @@ int duck_fleet_sense_delay(const duck_fleet_desc* desc, int N, uint64_t seed, in
 int duck_fleet_actuate_delayed(const duck_fleet_desc* desc, int N, uint64_t seed, int64_t robot_offset,
                                int32_t* lat_tick, const int32_t* lat, const float* action, float* ctl,
                                float* ctrl, void* stream);
+
+/* Following a recorded log: the robots are fed the actions a logged robot's policy gave, and every simulated
+ * observation is scored against the logged one, per robot and per column (the reference compares the two by eye:
+ * its loop and the robot both save what the policy saw, mujoco_infer.py:202, :241, and common/plot_saved_obs.py
+ * plots them side by side). In duck_policy_act's place: after duck_fleet_observe, [sense_delay] and [disturb],
+ * before duck_fleet_actuate or duck_fleet_actuate_delayed -- a robot's IMU delay and sensor noise are in the
+ * observation that is scored, its action delay acts on the fed action. No launch more than the loop with a
+ * policy; a loop without a log does not enqueue it.
+ *
+ * log [n_log][T][DUCK_FLEET_LOG_SIZE(nu)] row-major float32: row p of a log is the observation the logged
+ * robot's policy saw in period p (DUCK_FLEET_OBS_SIZE(nu) words in duck_fleet_observe's order), then the nu
+ * actions the policy answered with. log_id [N] int32 names each robot's log, clamped into [0, n_log - 1] as
+ * sched_id is. log_tick [N] int32 lives on the device, for tick's and lat_tick's reason: p = log_tick[e], a
+ * negative value read as 0 (set to 0 by the caller at the log's start). score [N][DUCK_FLEET_OBS_SIZE(nu)]
+ * float32, zeroed by the caller: the sum over the periods so far of the squared difference, per column.
+ *
+ * In this order, for robot e with row = log[min(max(log_id[e], 0), n_log - 1)]:
+ *   score    when p < T, for every obs column k whose log word r = row[p][k] is not a NaN:
+ *            d = obs[e][k] - r, q = d * d, score[e][k] = score[e][k] + q, each rounded on its own. A NaN in the
+ *            log marks a missing sample: that score word is not written (it keeps its bits). A NaN in the
+ *            simulated observation makes the score NaN, the right rank for such a model. alive is not looked at.
+ *   action   when p < T: action[e][a] = row[p][OBS + a], copied as uint32_t (NaN payloads and -0 keep their
+ *            bits); when p >= T: action[e][a] = +0.0.
+ *   command  when p + 1 < T: the 7 words of ctl.command = row[p + 1][6 .. 12], copied; they take effect in the
+ *            next period's observation, as a schedule's do. Otherwise the command is kept.
+ *   tick     log_tick[e] = min(p + 1, T), the kernel's last store for the robot.
+ * obs is read only. desc gives nu (the widths of ctl, obs and a log row). DUCK_EINVAL on n_log < 1 or T < 1.
+ * N == 0 launches nothing. */
+#define DUCK_FLEET_LOG_SIZE(nu) (17 + 7 * (nu)) /* an obs row, then the action that answered it */
+
+int duck_fleet_follow(const duck_fleet_desc* desc, int N, int n_log, int T, const float* log, const int32_t* log_id,
+                      int32_t* log_tick, const float* obs, float* score, float* ctl, float* action, void* stream);
 
 #ifdef __cplusplus
 }

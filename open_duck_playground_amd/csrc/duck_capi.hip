@@ -428,6 +428,47 @@ __global__ __launch_bounds__(FLEET_TPB) void fleet_actuate_delayed_kernel(const 
   if (a == 0) lat_tick[e] = (int)((uint32_t)p0 + 1u);
 }
 
+// Following a log (include/duck_fleet.h: duck_fleet_follow), the same 16-lane group per robot, in
+// duck_policy_act's place. The lanes stride over the observation columns, reading the log's row and the robot's
+// obs and score rows in runs of 16 consecutive words; lanes < nu carry the actions, lanes 0-6 the next period's
+// command. Log words travel as uint32_t: the actions and the command are copies, whatever the bits. Every lane
+// has read the tick (one load of the whole wave) before lane 0's store, which depends on it, can issue; it is
+// the kernel's last store. No LDS, no votes: lanes past the last robot leave.
+__global__ __launch_bounds__(FLEET_TPB) void fleet_follow_kernel(int nu, int n, int n_log, int T,
+                                                                 const uint32_t* __restrict__ log,
+                                                                 const int* __restrict__ log_id, int* log_tick,
+                                                                 const float* __restrict__ obs,
+                                                                 float* __restrict__ score, uint32_t* __restrict__ ctl,
+                                                                 uint32_t* __restrict__ action) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x % FLEET_TEAM;
+  const int e0 = blockIdx.x * (FLEET_TPB / FLEET_TEAM) + threadIdx.x / FLEET_TEAM;
+  if (e0 >= n) return;
+  const size_t e = e0;
+  const int O = DUCK_FLEET_OBS_SIZE(nu), W = DUCK_FLEET_LOG_SIZE(nu), C = DUCK_FLEET_CTL_SIZE(nu);
+  const int p0 = log_tick[e], p = p0 < 0 ? 0 : p0;
+  int id = log_id[e];
+  id = id < 0 ? 0 : (id > n_log - 1 ? n_log - 1 : id);
+  const bool inside = p < T;
+  // (row p of the robot's log; past the end the pointer is not formed from p, nor read)
+  const uint32_t* row = log + ((size_t)id * (size_t)T + (size_t)(inside ? p : 0)) * W;
+  if (inside) {
+    const float* o = obs + e * O;
+    float* s = score + e * O;
+    for (int k = lane; k < O; k += FLEET_TEAM) {
+      const float r = __uint_as_float(row[k]);
+      if (r == r) {
+        const float d = o[k] - r;
+        const float q = d * d;
+        s[k] = s[k] + q;
+      }
+    }
+  }
+  if (lane < nu) action[e * nu + lane] = inside ? row[O + lane] : 0u;
+  if (lane < 7 && p < T - 1) ctl[e * C + 5 * nu + lane] = row[W + 6 + lane];
+  if (lane == 0) log_tick[e] = inside ? p + 1 : T;
+}
+
 static const char* fleet_desc_error(const duck_fleet_desc* d) {
   if (d->nq < 1 || d->nv < 1 || d->nu < 1 || d->nu > DUCK_FLEET_MAX_NU) return "nq, nv >= 1 and 1 <= nu <= 16";
   for (int a = 0; a < d->nu; a++)
@@ -567,6 +608,22 @@ int duck_fleet_actuate_delayed(const duck_fleet_desc* d, int n, uint64_t seed, i
   const int per = FLEET_TPB / FLEET_TEAM;
   hipLaunchKernelGGL(fleet_actuate_delayed_kernel, dim3((n + per - 1) / per), dim3(FLEET_TPB), 0, (hipStream_t)stream,
                      *d, n, (unsigned long long)seed, (long long)robot_offset, lat_tick, lat, action, ctl, ctrl);
+  HIPCHECK(hipGetLastError());
+  return DUCK_OK;
+}
+
+int duck_fleet_follow(const duck_fleet_desc* d, int n, int n_log, int T, const float* log, const int32_t* log_id,
+                      int32_t* log_tick, const float* obs, float* score, float* ctl, float* action, void* stream) {
+  g_err.clear();
+  if (!d || !log || !log_id || !log_tick || !obs || !score || !ctl || !action)
+    return duck_fail(DUCK_EINVAL, "duck_fleet_follow: null pointer");
+  if (n < 0 || n > (1 << 27)) return duck_fail(DUCK_EINVAL, "duck_fleet_follow: bad size (0 <= N <= 2^27)");
+  if (n_log < 1 || T < 1) return duck_fail(DUCK_EINVAL, "duck_fleet_follow: a log needs n_log >= 1 and T >= 1");
+  if (const char* why = fleet_desc_error(d)) return duck_fail(DUCK_EINVAL, std::string("duck_fleet_follow: ") + why);
+  if (n == 0) return DUCK_OK;
+  const int per = FLEET_TPB / FLEET_TEAM;
+  hipLaunchKernelGGL(fleet_follow_kernel, dim3((n + per - 1) / per), dim3(FLEET_TPB), 0, (hipStream_t)stream, d->nu, n,
+                     n_log, T, (const uint32_t*)log, log_id, log_tick, obs, score, (uint32_t*)ctl, (uint32_t*)action);
   HIPCHECK(hipGetLastError());
   return DUCK_OK;
 }

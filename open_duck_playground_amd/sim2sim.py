@@ -293,7 +293,16 @@ class FleetInfer:
     its action, the actuator forces and the raw sensors -- and freezes a robot's ring ``post`` periods after
     the one in which it fell. Its counters live on the device, so it runs inside the captured graph.
     ``recorded(robot)`` returns the frames in period order; ``replay(robot, frame)`` returns a one-robot fleet
-    loaded from a recorded frame, whose next periods reproduce the robot's bit for bit."""
+    loaded from a recorded frame, whose next periods reproduce the robot's bit for bit.
+
+    Following a log (off by default; ``set_log(log, ids)`` or ``follow=(log, ids)``): duck_fleet_follow takes
+    duck_policy_act's place (no launch more): physics -> observe -> [sense_delay] -> [disturb] -> policy or follow
+    -> actuate or actuate_delayed -> [record]. The robots are fed the actions and commands of a recorded robot log,
+    and ``scores()`` / ``score_report()`` tell, per robot and observation column, how far the simulated observations
+    were from the logged ones: over randomised models and a delay grid, which model the logged robot moves like.
+    ``onnx_model_path=None`` is allowed with ``follow``: no policy is loaded. The start state is the loop's own (a log
+    that starts elsewhere is the caller's to load with ``load_state``), and joint-encoder latency is not modelled.
+    With no log set (``following()`` False) the loop enqueues exactly the launches above."""
 
     # control periods per captured graph (200 launches; 50 more with disturbances, 50 more with an IMU delay, 50 more
     # with a recorder: 400 at the most)
@@ -303,7 +312,7 @@ class FleetInfer:
                  reference_data: Optional[str] = None, standing: bool = False, device="cuda:0",
                  randomize: Optional[int] = None, command_schedule: Optional[tuple] = None,
                  pushes: Optional[tuple] = None, noise: Optional[tuple] = None, recorder: Optional[tuple] = None,
-                 robot_offset: int = 0, latency: Optional[tuple] = None):
+                 robot_offset: int = 0, latency: Optional[tuple] = None, follow: Optional[tuple] = None):
         import ctypes as C
 
         from .native import DuckError, check
@@ -312,12 +321,17 @@ class FleetInfer:
         n = self.num_robots = int(num_robots)
         if n < 1:
             raise DuckError("num_robots must be >= 1")
-        with open(onnx_model_path, "rb") as f:
-            pol = dense_policy(OnnxGraph(f.read()))
-        sizes = pol["sizes"]
-        if len(pol["W"]) > POLICY_ACT_MAX_LAYERS or max(sizes) > POLICY_ACT_MAX_WIDTH:
-            raise DuckError(f"policy layers {sizes} are outside duck_policy_act's limits (at most "
-                            f"{POLICY_ACT_MAX_LAYERS} layers, at most {POLICY_ACT_MAX_WIDTH} wide); there is no host fallback")
+        pol = None
+        if onnx_model_path is None:
+            if follow is None:
+                raise DuckError("a fleet needs a policy (onnx_model_path) or a log to follow (follow=(log, ids))")
+        else:
+            with open(onnx_model_path, "rb") as f:
+                pol = dense_policy(OnnxGraph(f.read()))
+            sizes = pol["sizes"]
+            if len(pol["W"]) > POLICY_ACT_MAX_LAYERS or max(sizes) > POLICY_ACT_MAX_WIDTH:
+                raise DuckError(f"policy layers {sizes} are outside duck_policy_act's limits (at most "
+                                f"{POLICY_ACT_MAX_LAYERS} layers, at most {POLICY_ACT_MAX_WIDTH} wide); there is no host fallback")
         self.env = Joystick(model_path, num_envs=n, device=device, use_imitation=False)
         m = self.model = self.env.mj_model
         self.device = dev = torch.device(device)
@@ -335,16 +349,18 @@ class FleetInfer:
         self.obs_size = fleet_obs_size(nu)
 
         # the policy's dense layers on the device, pointers in host arrays (duck_policy_act's arguments)
-        if sizes[0] != self.obs_size or pol["action_size"] != nu:
-            raise DuckError(f"policy maps {sizes[0]} -> {pol['action_size']}, the model's loop needs {self.obs_size} -> {nu}")
-        up = lambda a: None if a is None else torch.tensor(a, dtype=torch.float32, device=dev).contiguous()  # noqa: E731
-        self._W, self._b = [up(w) for w in pol["W"]], [up(b) for b in pol["b"]]
-        self._mean, self._istd = up(pol["mean"]), up(pol["istd"])
-        self._policy_args = (len(sizes) - 1, (C.c_int * len(sizes))(*sizes),
-                             (C.c_void_p * len(self._W))(*[w.data_ptr() for w in self._W]),
-                             (C.c_void_p * len(self._b))(*[b.data_ptr() for b in self._b]),
-                             None if self._mean is None else self._mean.data_ptr(),
-                             None if self._istd is None else self._istd.data_ptr())
+        self._policy_args = None        # no policy loaded: the fleet can only follow a log
+        if pol is not None:
+            if sizes[0] != self.obs_size or pol["action_size"] != nu:
+                raise DuckError(f"policy maps {sizes[0]} -> {pol['action_size']}, the model's loop needs {self.obs_size} -> {nu}")
+            up = lambda a: None if a is None else torch.tensor(a, dtype=torch.float32, device=dev).contiguous()  # noqa: E731
+            self._W, self._b = [up(w) for w in pol["W"]], [up(b) for b in pol["b"]]
+            self._mean, self._istd = up(pol["mean"]), up(pol["istd"])
+            self._policy_args = (len(sizes) - 1, (C.c_int * len(sizes))(*sizes),
+                                 (C.c_void_p * len(self._W))(*[w.data_ptr() for w in self._W]),
+                                 (C.c_void_p * len(self._b))(*[b.data_ptr() for b in self._b]),
+                                 None if self._mean is None else self._mean.data_ptr(),
+                                 None if self._istd is None else self._istd.data_ptr())
 
         z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)  # noqa: E731
         self.qpos, self.qvel = z(m.nq, n), z(m.nv, n)
@@ -370,6 +386,9 @@ class FleetInfer:
         self.lat = self.lat_tick = self.line = None
         self.lat_seed = self.lat_base = 0
         self.lat_sense = False
+        # following a log (include/duck_fleet.h duck_fleet_follow): off
+        self.log = self.log_id = self.log_tick = self.score = None
+        self.log_base = 0
         # the flight recorder (include/duck_fleet.h duck_fleet_record): off
         self.frame_fields = frame_fields(int(m.nq), int(m.nv), nu)
         self.ring = self.rec_head = self.rec_after = None
@@ -387,13 +406,15 @@ class FleetInfer:
             self.set_recorder(*recorder)
         if latency is not None:
             self.set_latency(*latency)
+        if follow is not None:
+            self.set_log(*follow)
 
     def restart(self) -> None:
         """Every robot back to the loop's start, with the randomisation record ``dr`` as it is now.
         MJInferBase.__init__: MjData at qpos0 with zero ctrl, one mj_step, then the home keyframe's qpos and
         ctrl (the velocity of that first step is kept); mujoco_infer.py:49-60 for the control record. The
-        period count goes back to 0, a command schedule to its segment 0, a recorder to no frames and a latency
-        to its first period (the delay line fills anew)."""
+        period count goes back to 0, a command schedule to its segment 0, a recorder to no frames, a latency
+        to its first period (the delay line fills anew) and a followed log to its row 0 with zero scores."""
         m, n = self.model, self.num_robots
         col = lambda a: torch.tensor(np.asarray(a, dtype=np.float32)[:, None], device=self.device)  # noqa: E731
         key = m.names["key"].index("home")
@@ -417,6 +438,11 @@ class FleetInfer:
         self.lat_base = 0
         if self.lat_tick is not None:
             self.lat_tick.zero_()
+        self.log_base = 0
+        if self.log is not None:
+            self.log_tick.zero_()
+            self.score.zero_()
+            self._log_command()    # row 0's command
 
     # --- launches -----------------------------------------------------------------------------
     def _stream(self):
@@ -441,7 +467,9 @@ class FleetInfer:
 
     def policy(self):
         """duck_policy_act on ``obs``."""
-        from .native import lib
+        from .native import DuckError, lib
+        if self._policy_args is None:
+            raise DuckError("no policy is loaded (onnx_model_path=None): the fleet can only follow a log (set_log)")
         P = lib()   # the policy kernel ships with libduck.so only, the rest with the model's library
         self._check(P.duck_policy_act(self.num_robots, *self._policy_args, self.obs.data_ptr(), None,
                                       self.action.data_ptr(), self._stream()), P)
@@ -454,8 +482,12 @@ class FleetInfer:
                                          self.ctl.data_ptr(), self.ctrl.data_ptr(), self._stream()), L)
 
     def act(self):
-        """duck_policy_act on ``obs``, then duck_fleet_actuate, or with a latency duck_fleet_actuate_delayed."""
-        self.policy()
+        """duck_policy_act on ``obs`` (following a log: duck_fleet_follow in its place), then duck_fleet_actuate,
+        or with a latency duck_fleet_actuate_delayed."""
+        if self.following():
+            self.follow()
+        else:
+            self.policy()
         if self.latent():
             self.actuate_delayed()
         else:
@@ -464,6 +496,19 @@ class FleetInfer:
     def latent(self) -> bool:
         """Whether a latency is set (duck_fleet_actuate_delayed in duck_fleet_actuate's place)."""
         return self.lat is not None
+
+    def following(self) -> bool:
+        """Whether a log is set (duck_fleet_follow in duck_policy_act's place)."""
+        return self.log is not None
+
+    def follow(self):
+        """duck_fleet_follow on this period's ``obs``: the score, the log's action, the next period's command, log_tick."""
+        import ctypes as C
+        L = self._lib
+        self._check(L.duck_fleet_follow(C.byref(self.desc), self.num_robots, int(self.log.shape[0]), int(self.log.shape[1]),
+                                        self.log.data_ptr(), self.log_id.data_ptr(), self.log_tick.data_ptr(),
+                                        self.obs.data_ptr(), self.score.data_ptr(), self.ctl.data_ptr(),
+                                        self.action.data_ptr(), self._stream()), L)
 
     def sense_delay(self):
         """duck_fleet_sense_delay on this period's ``obs``: the IMU columns into the delay line and, delayed, back."""
@@ -524,9 +569,17 @@ class FleetInfer:
     @torch.no_grad()
     def run(self, n_periods: int, record: bool = False):
         """``n_periods`` control periods for every robot. ``record=True`` returns the observations
-        [T][N][obs] the policy saw (a numpy array; such a run is eager)."""
+        [T][N][obs] the policy saw (a numpy array; such a run is eager). Following a log of T rows, a run that
+        would pass row T raises before anything is enqueued; so does one with neither a policy nor a log."""
+        from .native import DuckError
         from .ppo import check_device_error
         n_periods = int(n_periods)
+        if self.following():
+            done, T = self.periods_done - self.log_base, int(self.log.shape[1])
+            if done + n_periods > T:
+                raise DuckError(f"the log holds {T} periods and {done} are followed: {n_periods} more would pass its end")
+        elif self._policy_args is None:
+            raise DuckError("no policy is loaded and no log is set: nothing to run (set_log)")
         rec = torch.empty(n_periods, self.num_robots, self.obs_size, device=self.device) if record else None
         self.calls += 1
         self.periods_done += n_periods
@@ -582,6 +635,8 @@ class FleetInfer:
                 self.sched = self.sched_id = None
                 self.graph = None
             return
+        if self.log is not None:
+            raise DuckError("a log is being followed and writes the command itself: set_log(None) before a schedule")
         tab = np.asarray(table, dtype=np.float32)
         if tab.ndim != 3 or tab.shape[0] < 1 or tab.shape[1] < 1 or tab.shape[2] != 7:
             raise DuckError(f"a command schedule is [S][K][7] with S, K >= 1, got {tuple(tab.shape)}")
@@ -725,6 +780,77 @@ class FleetInfer:
         self.lat_seed, self.lat_base = int(seed) & 0xFFFFFFFFFFFFFFFF, self.periods_done
         self.lat_sense = bool((np.asarray(rows)[:, 3] > 0).any())
 
+    # --- following a log (include/duck_fleet.h duck_fleet_follow) ---------------------------------------
+    def set_log(self, log, ids=None) -> None:
+        """Follow a recorded robot log instead of the policy: ``log`` [T][W] or [L][T][W] float32, W =
+        DUCK_FLEET_LOG_SIZE(nu), row p the observation the logged robot's policy saw in period p and then the
+        action it answered with (``log_from_saved_obs``, ``load_log``); robot r follows log ``ids[r]`` ([N],
+        default r mod L). From now on ``act()`` enqueues duck_fleet_follow where it enqueued duck_policy_act: the
+        robots are fed the log's actions and commands, and ``score`` [N][obs] sums, per robot and column, the
+        squared distance of the simulated observation from the logged one (a NaN log word is a missing sample).
+        A robot's IMU delay and sensor noise are in what is scored, its action delay acts on the fed action.
+        The log starts anew when set: ``log_tick`` and ``score`` zeroed, row 0's command written
+        (``log_base`` = the periods run since ``restart()``). The loop's start state is its own: a log that starts
+        elsewhere is the caller's to load with ``load_state``. A log rewritten with the same shape keeps the
+        captured graph. A command schedule and a log both write the command: setting both raises. ``log=None``
+        turns the mode off (the commands stay)."""
+        n = self.num_robots
+        if log is None:
+            if self.log is not None:
+                self.log = self.log_id = self.log_tick = self.score = None
+                self.graph = None
+            return
+        tab, idv = log_arguments(log, ids, n, self.num_dofs, scheduled=self.sched is not None)
+        if self.log is None or tuple(self.log.shape) != tab.shape:    # new buffers, or sizes the captured launch took by value
+            self.log = torch.empty(tab.shape, dtype=torch.float32, device=self.device)
+            self.log_id = torch.empty(n, dtype=torch.int32, device=self.device)
+            self.log_tick = torch.zeros(n, dtype=torch.int32, device=self.device)
+            self.score = torch.zeros(n, self.obs_size, dtype=torch.float32, device=self.device)
+            self.graph = None
+        self.log.copy_(torch.as_tensor(tab))
+        self.log_id.copy_(torch.as_tensor(idv))
+        self.log_tick.zero_()
+        self.score.zero_()
+        self.log_base = self.periods_done
+        self._log_command()
+
+    def _log_command(self) -> None:
+        """``ctl.command`` = columns 6-12 of the log's row of the current log_tick (row 0 after ``set_log``)."""
+        row = torch.clamp(self.log_tick.long(), min=0, max=int(self.log.shape[1]) - 1)
+        self.ctl_field("command").copy_(self.log[self.log_id.long(), row, 6:13])
+
+    def scores(self) -> np.ndarray:
+        """``score`` [N][obs] float32: per robot and obs column, the sum over the periods followed of the squared
+        difference between the simulated and the logged observation."""
+        from .native import DuckError
+        if self.log is None:
+            raise DuckError("no log is set (set_log)")
+        torch.cuda.synchronize(self.device)
+        return self.score.cpu().numpy()
+
+    def score_report(self, weights=None) -> Dict[str, np.ndarray]:
+        """Per robot, the rms distance from its log per column group (``score_groups``: gyro, accelerometer,
+        joint_position, joint_velocity, action_history, motor_targets, contacts, phase), ``"total"``, the sum of
+        weight x rms over the groups (``weights``: {group: weight}, default 1 on the four sensor groups, 0 on the
+        rest), and ``"periods"``, the rows followed. A group's count is the log's own non-NaN words in its columns
+        over the rows followed (``score_report``, the module's function). The action-history and motor-target
+        groups are checks of the feeding, not of the model: they compare what the loop fed with what the log says
+        was fed, and are 0 unless the log is inconsistent with itself or an action delay moved the targets."""
+        score = self.scores()
+        return score_report(score, self.log.cpu().numpy(), self.log_id.cpu().numpy(), self.log_tick.cpu().numpy(), weights)
+
+    def save_log(self, path: str) -> None:
+        """The log being followed to ``path`` (``save_log``, the module's function)."""
+        from .native import DuckError
+        if self.log is None:
+            raise DuckError("no log is set (set_log)")
+        save_log(path, self.log.cpu().numpy())
+
+    @staticmethod
+    def load_log(path: str) -> np.ndarray:
+        """A log from ``path`` (``load_log``, the module's function), for ``set_log``."""
+        return load_log(path)
+
     # --- the flight recorder (include/duck_fleet.h duck_fleet_record) ----------------------------------
     def set_recorder(self, depth: Optional[int], post: int = 0) -> None:
         """Keep every robot's last ``depth`` control periods on the device, frozen ``post`` periods after the
@@ -772,6 +898,8 @@ class FleetInfer:
         the robot's randomisation record, schedule, push row and latency row, and its global id in the disturbance
         and latency streams. With an IMU delay the delay line is rebuilt from the raw sensors of the frame and of
         the one before it; a robot whose IMU delay reaches 2 cannot be replayed from the oldest frame it holds.
+        Of a following fleet the replay carries the robot's log and ``log_tick`` at the frame's period (its scores
+        start at zero).
         The loop is a pure function of what a frame holds, that record and that stream, so running the replay
         k periods reproduces the k periods the robot ran after that frame, bit for bit. The fleet's settings
         are taken as they are now: they must not have changed since the frame was written."""
@@ -781,8 +909,11 @@ class FleetInfer:
             raise DuckError(f"robot {robot} holds {len(frames)} frames, got frame {frame!r}")
         robot = int(robot)
         f, p = torch.tensor(frames[int(frame)], device=self.device), int(period[int(frame)])
+        follow = None
+        if self.following():   # the robot's own log (before the frame: set_log writes a command)
+            follow = (self.log[int(self.log_id[robot])].cpu().numpy(), None)
         r = FleetInfer(num_robots=1, randomize=None if self.dr is None else 0,
-                       robot_offset=self.robot_offset + robot, **self._made_from)
+                       robot_offset=self.robot_offset + robot, follow=follow, **self._made_from)
         if self.dr is not None:
             r.dr.copy_(self.dr.view(-1, self.num_robots)[:, robot])
         # the disturbances first, the frame last: set_command_schedule writes a command
@@ -799,6 +930,12 @@ class FleetInfer:
         r.ctrl[:, 0].copy_(r.ctl_field("motor_targets")[0])
         if self.disturbed():   # the device's period count at that frame: it has advanced once per period since
             r.tick.copy_(self.tick[robot:robot + 1] - (self.periods_done - p))
+        if self.following():   # log_tick once the frame's period was done, as tick; the scores start at zero
+            after = int(self.log_tick[robot]) - (self.periods_done - p)
+            if p < self.log_base:
+                raise DuckError(f"frame {frame!r} of robot {robot} was written before the log was set")
+            r.log_tick.fill_(after)
+            r.log_base = p - after
         if self.latent():
             row = self.lat[robot:robot + 1].cpu().numpy()
             r._load_latency(row, self.lat_seed)
@@ -1104,10 +1241,280 @@ def falls_archive(fleet: "FleetInfer", max_robots: int) -> Dict[str, np.ndarray]
     return out
 
 
+# --- following a log (include/duck_fleet.h duck_fleet_follow) -------------------------------------------
+def fleet_log_size(nu: int) -> int:
+    """DUCK_FLEET_LOG_SIZE(nu): the width of a log row, an obs row and then the action that answered it."""
+    return HEADERS.value(f"DUCK_FLEET_LOG_SIZE({int(nu)})")
+
+
+def log_arguments(log, ids, num_robots: int, nu: int, scheduled: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+    """``FleetInfer.set_log``'s arguments, validated on the host: (log [L][T][W] float32 C-contiguous, ids [N]
+    int32). DuckError on a command schedule set at the same time (``scheduled``: both write the command), a shape
+    that is not [T][W] or [L][T][W] with L, T >= 1 and W = DUCK_FLEET_LOG_SIZE(nu), and ids that are not [N]
+    integers in [0, L). NaN words are data: a NaN observation word is a missing sample."""
+    from .native import DuckError
+    n, W = int(num_robots), fleet_log_size(nu)
+    if scheduled:
+        raise DuckError("a command schedule is set and a log writes the command itself: set_command_schedule(None) first")
+    try:
+        tab = np.ascontiguousarray(log, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise DuckError("a log is a float32 array [T][W] or [L][T][W]") from None
+    if tab.ndim == 2:
+        tab = tab[None]
+    if tab.ndim != 3 or tab.shape[2] != W:
+        raise DuckError(f"a log is [T][{W}] or [L][T][{W}] ({fleet_obs_size(nu)} obs words, then {int(nu)} actions), "
+                        f"got {tuple(np.shape(log))}")
+    if tab.shape[0] < 1 or tab.shape[1] < 1:
+        raise DuckError(f"a log needs L >= 1 logs of T >= 1 rows, got {tuple(tab.shape)}")
+    if tab.shape[1] >= 2 ** 31 - 1 or tab.shape[0] >= 2 ** 31 - 1:
+        raise DuckError("a log's L and T must fit an int32")
+    idv = np.arange(n) % tab.shape[0] if ids is None else np.asarray(ids)
+    if idv.shape != (n,) or not np.issubdtype(idv.dtype, np.integer):
+        raise DuckError(f"log ids must be [{n}] integers, got {idv.dtype} {tuple(idv.shape)}")
+    if idv.min() < 0 or idv.max() >= tab.shape[0]:
+        raise DuckError(f"log ids must lie in [0, {tab.shape[0]}), got [{idv.min()}, {idv.max()}]")
+    return tab, idv.astype(np.int32)
+
+
+def _obs_nu(width: int) -> int:
+    from .native import DuckError
+    nu, rest = divmod(int(width) - 17, 6)
+    if rest or nu < 1:
+        raise DuckError(f"an observation row is 17 + 6 nu words wide, got {width}")
+    return nu
+
+
+def log_from_saved_obs(obs) -> np.ndarray:
+    """The reference's ``saved_obs`` form -- [T + 1][OBS] (or [L][T + 1][OBS]), the observations a loop's policy
+    saw period by period (mujoco_infer.py:202, :241; ``FleetInfer.run(record=True)[:, robot]``) -- as a log of T
+    rows: row p is observation p, then action p, which is the ``last_action`` columns of observation p + 1 (the
+    action the policy answered observation p with). Words are copied, whatever their bits."""
+    from .native import DuckError
+    a = np.ascontiguousarray(obs, dtype=np.float32)
+    if a.ndim not in (2, 3) or a.shape[-2] < 2:
+        raise DuckError(f"saved observations are [T + 1][OBS] or [L][T + 1][OBS] with T >= 1, got {tuple(a.shape)}")
+    nu = _obs_nu(a.shape[-1])
+    last = 13 + 2 * nu          # gyro 3, accelerometer 3, command 7, joint angles nu, joint velocities nu
+    return np.ascontiguousarray(np.concatenate([a[..., :-1, :], a[..., 1:, last:last + nu]], axis=-1))
+
+
+def saved_obs_from_log(log) -> np.ndarray:
+    """``log_from_saved_obs`` the other way, for a log whose actions are the ``last_action`` columns of its next
+    row: [T + 1][OBS], the last row NaN (no sample) but for its ``last_action`` columns. DuckError for a log that
+    does not have that form (it cannot be held as observation rows alone)."""
+    from .native import DuckError
+    a = np.ascontiguousarray(log, dtype=np.float32)
+    nu, rest = divmod(a.shape[-1] - 17, 7) if a.ndim in (2, 3) else (0, 1)
+    if rest or nu < 1 or a.shape[-2] < 1:
+        raise DuckError(f"a log is [T][17 + 7 nu] or [L][T][17 + 7 nu] with T >= 1, got {tuple(a.shape)}")
+    O, last = 17 + 6 * nu, 13 + 2 * nu
+    if a[..., :-1, O:].view(np.int32).tobytes() != a[..., 1:, last:last + nu].view(np.int32).tobytes():
+        raise DuckError("the log's actions are not the last_action columns of its next rows: it is not a saved_obs "
+                        "form, save it as .npz (obs and action)")
+    end = np.full(a.shape[:-2] + (1, O), np.nan, dtype=np.float32)
+    end[..., 0, last:last + nu] = a[..., -1, O:]
+    return np.ascontiguousarray(np.concatenate([a[..., :O], end], axis=-2))
+
+
+def save_log(path: str, log) -> None:
+    """A log ([T][W] or [L][T][W]) to ``path``: ``.npz`` holds ``obs`` [..][T][OBS] and ``action`` [..][T][nu], any
+    log; ``.npy`` holds the observation rows alone, the reference's saved_obs form [..][T + 1][OBS]
+    (``saved_obs_from_log``: only a log whose actions are its next rows' ``last_action`` columns)."""
+    from .native import DuckError
+    a = np.ascontiguousarray(log, dtype=np.float32)
+    if path.endswith(".npy"):
+        np.save(path, saved_obs_from_log(a), allow_pickle=False)
+    elif path.endswith(".npz"):
+        nu, rest = divmod(a.shape[-1] - 17, 7) if a.ndim in (2, 3) else (0, 1)
+        if rest or nu < 1:
+            raise DuckError(f"a log is [T][17 + 7 nu] or [L][T][17 + 7 nu], got {tuple(a.shape)}")
+        np.savez(path, obs=a[..., :17 + 6 * nu], action=a[..., 17 + 6 * nu:])
+    else:
+        raise DuckError(f"a log file is .npy or .npz, got {path!r}")
+
+
+def load_log(path: str) -> np.ndarray:
+    """A log from ``path``. ``.npy``: the observation rows [T + 1][OBS] (or [L][T + 1][OBS]) of a saved_obs
+    (``log_from_saved_obs``). ``.npz``: ``obs`` and, optionally, ``action`` [..][T][nu] of the same leading shape;
+    without ``action``, ``obs`` is the saved_obs form again. Pickles are not read: the reference pickles its
+    saved_obs list (mujoco_infer.py:241), and the one-line conversion on the user's side is
+    ``np.save("log.npy", np.asarray(pickle.load(open("saved_obs.pkl", "rb")), dtype=np.float32))``."""
+    from .native import DuckError
+    if path.endswith(".npy"):
+        return log_from_saved_obs(np.load(path, allow_pickle=False))
+    if not path.endswith(".npz"):
+        raise DuckError(f"a log file is .npy or .npz (pickles are not read), got {path!r}")
+    with np.load(path, allow_pickle=False) as z:
+        if "obs" not in z.files:
+            raise DuckError(f"{path!r} holds no array 'obs' (it holds {z.files})")
+        obs = np.ascontiguousarray(z["obs"], dtype=np.float32)
+        if "action" not in z.files:
+            return log_from_saved_obs(obs)
+        act = np.ascontiguousarray(z["action"], dtype=np.float32)
+    if obs.ndim not in (2, 3) or act.shape != obs.shape[:-1] + (_obs_nu(obs.shape[-1]),):
+        raise DuckError(f"'obs' [..][T][17 + 6 nu] and 'action' [..][T][nu] do not fit: {tuple(obs.shape)}, {tuple(act.shape)}")
+    return np.ascontiguousarray(np.concatenate([obs, act], axis=-1))
+
+
+SENSOR_GROUPS = ("gyro", "accelerometer", "joint_position", "joint_velocity")   # weight 1 by default
+
+
+def score_groups(nu: int) -> Dict[str, Tuple[int, int]]:
+    """(first obs column, width) of each scored column group. The command columns (6-12) are fed from the log and
+    belong to none."""
+    return {"gyro": (0, 3), "accelerometer": (3, 3), "joint_position": (13, nu), "joint_velocity": (13 + nu, nu),
+            "action_history": (13 + 2 * nu, 3 * nu), "motor_targets": (13 + 5 * nu, nu), "contacts": (13 + 6 * nu, 2),
+            "phase": (15 + 6 * nu, 2)}
+
+
+def score_weights(weights=None, nu: int = 1) -> Dict[str, float]:
+    """{group: weight} over every group of ``score_groups``: 1 on the four sensor groups and 0 on the rest, then
+    ``weights`` ({group: weight}) over that. DuckError on an unknown group or a weight that is not finite."""
+    from .native import DuckError
+    out = {g: (1.0 if g in SENSOR_GROUPS else 0.0) for g in score_groups(nu)}
+    for g, w in (weights or {}).items():
+        if g not in out:
+            raise DuckError(f"no score group {g!r} (the groups: {', '.join(out)})")
+        if not np.isfinite(w):
+            raise DuckError(f"the weight of {g!r} must be finite, got {w!r}")
+        out[g] = float(w)
+    return out
+
+
+def score_report(score, log, log_id, log_tick, weights=None) -> Dict[str, np.ndarray]:
+    """``FleetInfer.score_report`` on host arrays: score [N][OBS], log [L][T][W], log_id [N], log_tick [N] (the rows
+    each robot has followed). Per group [N] float64: sqrt(sum of the group's score words / count), the count being
+    the non-NaN log words of the group's columns in rows 0 .. log_tick - 1 of the robot's log (NaN when that is 0);
+    ``"total"`` = sum of weight x rms over the groups with a non-zero weight and a count (a robot with a NaN score
+    has a NaN total, and so has one with no such group: they rank last), and ``"periods"``. The action_history and motor_targets groups are checks of
+    the feeding, not of the model."""
+    score = np.asarray(score, dtype=np.float64)
+    log = np.asarray(log, dtype=np.float32)
+    log = log[None] if log.ndim == 2 else log
+    n, O = score.shape
+    nu = _obs_nu(O)
+    T = log.shape[1]
+    ids = np.clip(np.asarray(log_id, dtype=np.int64), 0, log.shape[0] - 1)
+    rows = np.clip(np.asarray(log_tick, dtype=np.int64), 0, T)
+    present = np.concatenate([np.zeros((log.shape[0], 1, O), np.int64),
+                              np.cumsum(~np.isnan(log[:, :, :O]), axis=1, dtype=np.int64)], axis=1)   # [L][T + 1][OBS]
+    count = present[ids, rows]                                                                       # [N][OBS]
+    w = score_weights(weights, nu)
+    out, total, counted = {}, np.zeros(n), np.zeros(n, bool)
+    for g, (o, width) in score_groups(nu).items():
+        c = count[:, o:o + width].sum(1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out[g] = np.sqrt(score[:, o:o + width].sum(1) / np.where(c > 0, c, np.nan))
+        if w[g] != 0.0:
+            total = total + np.where(c > 0, w[g] * out[g], 0.0)
+            counted |= c > 0
+    out["total"], out["periods"] = np.where(counted, total, np.nan), rows   # nothing compared: no rank
+    return out
+
+
+def rank_totals(total) -> np.ndarray:
+    """Robot ids from the best (smallest) total to the worst, ties by id; NaN totals last."""
+    t = np.asarray(total, dtype=np.float64)
+    return np.lexsort((np.arange(len(t)), np.where(np.isnan(t), np.inf, t), np.isnan(t)))
+
+
+def refine_population(dr, total, elite: int, rng, lo, hi) -> np.ndarray:
+    """The next round's randomisation record of a search over the randomisation box. ``dr`` [R][N] float32 (a
+    column per robot, ``FleetInfer.dr.view(-1, N)``), ``total`` [N] the robots' score totals. The ``elite`` best
+    columns (``rank_totals``: NaN last) are kept unchanged, as columns 0 .. elite - 1 in rank order; every other
+    column is drawn per row from a normal with the elite's mean and standard deviation (``rng``: a
+    numpy.random.Generator) and clipped to [``lo``, ``hi``] ([R] each: the per-row minimum and maximum of round 0's
+    duck_randomize population, so the search never leaves the box that was randomised). The rows are drawn
+    independently: a correlation between rows of the elite is not kept. Pure numpy; returns [R][N] float32."""
+    from .native import DuckError
+    dr = np.asarray(dr, dtype=np.float32)
+    total = np.asarray(total, dtype=np.float64)
+    if dr.ndim != 2 or total.shape != (dr.shape[1],):
+        raise DuckError(f"dr is [R][N] and total [N], got {tuple(dr.shape)} and {tuple(total.shape)}")
+    R, n = dr.shape
+    lo, hi = np.asarray(lo, dtype=np.float32), np.asarray(hi, dtype=np.float32)
+    if int(elite) != elite or not 1 <= int(elite) <= n:
+        raise DuckError(f"elite must be an integer in [1, {n}], got {elite!r}")
+    if lo.shape != (R,) or hi.shape != (R,) or not (lo <= hi).all():
+        raise DuckError(f"lo and hi are [{R}] with lo <= hi")
+    elite = int(elite)
+    best = dr[:, rank_totals(total)[:elite]]
+    mean, std = best.astype(np.float64).mean(1), best.astype(np.float64).std(1)
+    draw = mean[:, None] + std[:, None] * rng.standard_normal((R, n - elite))
+    draw = np.minimum(np.maximum(draw.astype(np.float32), lo[:, None]), hi[:, None])
+    return np.ascontiguousarray(np.concatenate([best, draw], axis=1), dtype=np.float32)
+
+
+def add_follow_arguments(p) -> None:
+    p.add_argument("--follow", type=str, default=None, metavar="LOG",
+                   help="follow a recorded robot log (.npy obs rows, or .npz obs + action) instead of a policy and "
+                        "score every robot's observations against it")
+    p.add_argument("--follow_weights", type=str, default=None, metavar="g=w,...",
+                   help="weights of the score groups in the total (default: 1 on gyro, accelerometer, joint_position, "
+                        "joint_velocity)")
+    p.add_argument("--rounds", type=int, default=1, metavar="R",
+                   help="rounds of the search: round 0 is --randomize SEED, each later one refines around the best")
+    p.add_argument("--elite", type=int, default=8, metavar="K", help="the best K robots a round keeps and reports")
+    p.add_argument("--fit_out", type=str, default=None, metavar="fit.json", help="write the last round's best robots")
+
+
+def follow_plan(args):
+    """The command line's follow flags, or None without ``--follow``: {"log": the path, "weights": {group: weight}
+    as given, "rounds", "elite" (at most num_robots), "fit_out"}. ValueError on a flag that needs ``--follow``, a bad
+    weight list, ``--rounds`` < 1, ``--elite`` < 1, or more than one round without ``--randomize``."""
+    if args.follow is None:
+        if args.follow_weights is not None or args.rounds != 1 or args.fit_out is not None:
+            raise ValueError("--follow_weights, --rounds and --fit_out need --follow LOG")
+        return None
+    weights = {}
+    for item in (args.follow_weights or "").split(","):
+        if not item.strip():
+            continue
+        try:
+            g, w = item.split("=")
+            weights[g.strip()] = float(w)
+            assert g.strip() in score_groups(1) and np.isfinite(weights[g.strip()])
+        except Exception:
+            raise ValueError(f"--follow_weights wants group=weight,... over {', '.join(score_groups(1))}, got {item!r}") from None
+    if args.rounds < 1 or args.elite < 1:
+        raise ValueError("--rounds and --elite must be >= 1")
+    if args.rounds > 1 and args.randomize is None:
+        raise ValueError("--rounds above 1 searches the randomisation box: it needs --randomize SEED")
+    if args.resample_commands:
+        raise ValueError("--resample_commands and --follow both write the command")
+    return {"log": args.follow, "weights": weights, "rounds": int(args.rounds),
+            "elite": min(int(args.elite), int(args.num_robots)), "fit_out": args.fit_out}
+
+
+def follow_round(fleet: "FleetInfer", rep: Dict[str, np.ndarray], survived, elite: int, delays=None) -> dict:
+    """One round of the report's ``"follow"`` key: the best total and, for the best ``elite`` robots, the id, the
+    group rms values, the total, the periods survived, the delay cell (with a delay grid) and the randomisation
+    record by ``cabi.dr_layout``'s field names (with ``--randomize``)."""
+    num = lambda v: None if np.isnan(v) else float(v)  # noqa: E731
+    order = rank_totals(rep["total"])[:elite]
+    dr = None if fleet.dr is None else fleet.dr.view(-1, fleet.num_robots).cpu().numpy()
+    layout = dr_layout(fleet.model.nbody, fleet.num_dofs)
+    names = [k for k in layout if k != "nfloat"]
+    best = []
+    for e in order:
+        row = {"id": int(e), "total": num(rep["total"][e]), "rms": {g: num(rep[g][e]) for g in score_groups(fleet.num_dofs)},
+               "periods_followed": int(rep["periods"][e]), "periods_survived": int(survived[e])}
+        if delays is not None:
+            c = int(delays["cell"][e])
+            row["delay_cell"] = {"cell": c, "action_delay": int(delays["cells"][c][0]), "sense_delay": int(delays["cells"][c][1])}
+        if dr is not None:
+            ends = [layout[k] for k in names[1:]] + [layout["nfloat"]]
+            row["randomization"] = {k: [float(v) for v in dr[layout[k]:end, e]] for k, end in zip(names, ends)}
+        best.append(row)
+    return {"best_total": best[0]["total"], "best": best}
+
+
 def build_parser():
     import argparse
     p = argparse.ArgumentParser(description="Run an exported policy in the deployment loop for a fleet of robots")
-    p.add_argument("-o", "--onnx_model_path", type=str, required=True)
+    p.add_argument("-o", "--onnx_model_path", type=str, default=None,
+                   help="the exported policy (optional with --follow LOG)")
     p.add_argument("--reference_data", type=str, default=None)
     p.add_argument("--model_path", type=str, default="flat_terrain")
     p.add_argument("--standing", action="store_true", default=False)
@@ -1120,6 +1527,7 @@ def build_parser():
     add_disturbance_arguments(p)
     add_latency_arguments(p)
     add_recorder_arguments(p)
+    add_follow_arguments(p)
     return p
 
 
@@ -1127,6 +1535,12 @@ def parse_arguments(argv=None):
     """The command line's arguments; a flag that needs another one is a usage error."""
     p = build_parser()
     args = p.parse_args(argv)
+    if args.onnx_model_path is None and args.follow is None:
+        p.error("-o/--onnx_model_path is required (unless --follow LOG is given)")
+    try:
+        follow_plan(args)
+    except ValueError as e:
+        p.error(str(e))
     if args.record_falls is None and args.record_out is not None:
         p.error("--record_out needs --record_falls DEPTH")
     if args.record_falls is not None and (args.record_falls < 1 or args.record_post < 0 or args.record_max < 0):
@@ -1141,9 +1555,15 @@ def main(argv=None) -> int:
     plan = disturbance_plan(args, cells)
     n_push = 1 if plan is None or plan["push_cells"] is None else len(plan["push_cells"])
     delays = latency_plan(args, len(cells), n_push)
+    following = follow_plan(args)
+    log = None if following is None else load_log(following["log"])
+    if log is not None:
+        args.periods = min(args.periods, int(log.shape[-2]))      # a run cannot pass the log's end
     fleet = FleetInfer(args.model_path, args.onnx_model_path, args.num_robots, reference_data=args.reference_data,
-                       standing=args.standing, device=args.device, randomize=args.randomize)
-    fleet.set_commands(cells[np.arange(args.num_robots) % len(cells)])
+                       standing=args.standing, device=args.device, randomize=args.randomize,
+                       follow=None if log is None else (log, None))
+    if log is None:            # (a followed log brings its own commands)
+        fleet.set_commands(cells[np.arange(args.num_robots) % len(cells)])
     if plan is not None:
         if plan["schedule"] is not None:
             fleet.set_command_schedule(*plan["schedule"])
@@ -1158,6 +1578,30 @@ def main(argv=None) -> int:
     t0 = time.time()
     fleet.run(args.periods)
     dt = time.time() - t0
+    follow_doc = None
+    if following is not None:
+        # system identification by search: score, keep the best, draw the next population around them, run again
+        n, elite = args.num_robots, following["elite"]
+        weights = score_weights(following["weights"], fleet.num_dofs)
+        follow_doc = {"log": following["log"], "log_rows": int(log.shape[-2]), "periods": args.periods, "weights": weights,
+                      "elite": elite, "rounds": []}
+        rng = np.random.default_rng(args.randomize)
+        box = None if fleet.dr is None else fleet.dr.view(-1, n).cpu().numpy()
+        for rnd in range(following["rounds"]):
+            if rnd > 0:
+                order = rank_totals(srep["total"])
+                new = refine_population(fleet.dr.view(-1, n).cpu().numpy(), srep["total"], elite, rng, box.min(1), box.max(1))
+                fleet.dr.copy_(torch.as_tensor(new.reshape(-1)))
+                if delays is not None:     # an elite robot keeps its delay cell, a new one draws an elite's
+                    cell = delays["cell"][order[:elite]]
+                    cell = delays["cell"] = np.concatenate([cell, rng.choice(cell, n - elite)])
+                    a, s = delays["cells"][cell, 0], delays["cells"][cell, 1]
+                    zero = np.zeros_like(a)
+                    fleet.set_latency(*(((zero, a), (zero, s)) if args.delay_jitter else (a, s)), args.delay_seed)
+                fleet.restart()
+                fleet.run(args.periods)
+            srep = fleet.score_report(weights)
+            follow_doc["rounds"].append({"round": rnd, **follow_round(fleet, srep, fleet.report()["periods"], elite, delays)})
     rep = fleet.report()
     rows = grid_report(rep, fleet.acc.cpu().numpy(), cells, args.periods)
     doc = {"model_path": args.model_path, "onnx_model_path": args.onnx_model_path, "num_robots": args.num_robots,
@@ -1182,6 +1626,12 @@ def main(argv=None) -> int:
             written = int(len(arrays["robots"]))
         doc["recorder"] = {"depth": args.record_falls, "post": args.record_post, "fallen": int(rep["fell"].sum()),
                            "written": written}
+    if follow_doc is not None:
+        doc["follow"] = follow_doc
+        if following["fit_out"]:
+            with open(following["fit_out"], "w") as f:
+                f.write(json.dumps({**{k: v for k, v in follow_doc.items() if k != "rounds"}, "model_path": args.model_path,
+                                    "randomize": args.randomize, **follow_doc["rounds"][-1]}, indent=1) + "\n")
     text = json.dumps(doc, indent=1)
     if args.out:
         with open(args.out, "w") as f:
