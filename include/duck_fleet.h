@@ -72,7 +72,15 @@ typedef struct {
  *   5nu+8          phase_frequency_factor
  *   5nu+9, 5nu+10  imitation_phase (cos, sin)
  * The reference starts with zero actions, both targets at default_actuator, a zero command, imitation_i 0,
- * factor 1 and phase (0, 0) (mujoco_infer.py:49-60). */
+ * factor 1 and phase (0, 0) (mujoco_infer.py:49-60).
+ * The first word of each field (each macro in its own arguments only, as the sizes are): */
+#define DUCK_FLEET_CTL_ACTION(nu, d) ((d) * (nu)) /* history entry d = 0, 1, 2: last_action, last_last_action, ... */
+#define DUCK_FLEET_CTL_MOTOR_TARGETS(nu) (3 * (nu))
+#define DUCK_FLEET_CTL_PREV_MOTOR_TARGETS(nu) (4 * (nu))
+#define DUCK_FLEET_CTL_COMMAND(nu) (5 * (nu))
+#define DUCK_FLEET_CTL_IMITATION_I(nu) (5 * (nu) + 7)
+#define DUCK_FLEET_CTL_PHASE_FREQUENCY_FACTOR(nu) (5 * (nu) + 8)
+#define DUCK_FLEET_CTL_IMITATION_PHASE(nu) (5 * (nu) + 9)
 #define DUCK_FLEET_CTL_SIZE(nu) (5 * (nu) + 11)
 /* obs [N][DUCK_FLEET_OBS_SIZE(nu)] row-major; acc [N][DUCK_FLEET_ACC_SIZE] row-major */
 #define DUCK_FLEET_OBS_SIZE(nu) (17 + 6 * (nu))

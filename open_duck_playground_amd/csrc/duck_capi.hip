@@ -109,6 +109,15 @@ __device__ __forceinline__ float fleet_div_rn(float x, float y) {
   return fmaf(fmaf(-q, y, x), r, q);
 }
 
+// A thread's place: its lane of the 16-lane group and the group's robot; false when the group is past robot
+// n - 1 and leaves. (fleet_observe_kernel, whose groups past the end stay for the votes, places itself.)
+__device__ __forceinline__ bool fleet_place(int n, int& lane, size_t& e) {
+  lane = threadIdx.x % FLEET_TEAM;
+  const int e0 = blockIdx.x * (FLEET_TPB / FLEET_TEAM) + threadIdx.x / FLEET_TEAM;
+  e = e0;
+  return e0 < n;
+}
+
 __global__ __launch_bounds__(FLEET_TPB) void fleet_observe_kernel(const duck_fleet_desc D, int n,
                                                                   const float* __restrict__ qpos,
                                                                   const float* __restrict__ qvel,
@@ -126,10 +135,11 @@ __global__ __launch_bounds__(FLEET_TPB) void fleet_observe_kernel(const duck_fle
   const float* sens = aux + (size_t)D.sens_off * N + e;
 
   // mujoco_infer.py:175-197
-  float ii = c[5 * nu + 7], ph0 = c[5 * nu + 9], ph1 = c[5 * nu + 10];
+  float ii = c[DUCK_FLEET_CTL_IMITATION_I(nu)], ph0 = c[DUCK_FLEET_CTL_IMITATION_PHASE(nu)],
+        ph1 = c[DUCK_FLEET_CTL_IMITATION_PHASE(nu) + 1];
   if (!D.standing) {
     const float nb = (float)D.nb_steps_in_period;
-    ii = fmodf(ii + c[5 * nu + 8], nb);
+    ii = fmodf(ii + c[DUCK_FLEET_CTL_PHASE_FREQUENCY_FACTOR(nu)], nb);
     const float a = fleet_div_rn(ii, nb) * 6.2831855f;
     ph0 = cosf(a);
     ph1 = sinf(a);
@@ -157,13 +167,13 @@ __global__ __launch_bounds__(FLEET_TPB) void fleet_observe_kernel(const duck_fle
       v = sens[(size_t)(D.accelerometer + j) * N];
       if (j == 0) v = v + D.accel_x_offset;
     } else if ((j -= 3) < 7) {
-      v = c[5 * nu + j];
+      v = c[DUCK_FLEET_CTL_COMMAND(nu) + j];
     } else if ((j -= 7) < nu) {
       v = qpos[(size_t)D.act_qpos[j] * N + e] - D.act_default[j];
     } else if ((j -= nu) < nu) {
       v = qvel[(size_t)D.act_dof[j] * N + e] * D.dof_vel_scale;
     } else if ((j -= nu) < 4 * nu) {
-      v = c[j];  // the three past actions, then the motor targets: the record's order
+      v = c[j];  // the three past actions, then the motor targets: relies on the record's order, [0, 4 nu)
     } else if ((j -= 4 * nu) < 2) {
       v = ((feet >> (4 * j)) & 0xfu) ? 1.f : 0.f;
     } else {
@@ -180,7 +190,8 @@ __global__ __launch_bounds__(FLEET_TPB) void fleet_observe_kernel(const duck_fle
         alive[e] = 0.f;
       } else {
         float* r = acc + e * DUCK_FLEET_ACC_SIZE;
-        const float dx = vx - c[5 * nu], dy = vy - c[5 * nu + 1], dz = wz - c[5 * nu + 2];
+        const int cmd = DUCK_FLEET_CTL_COMMAND(nu);
+        const float dx = vx - c[cmd], dy = vy - c[cmd + 1], dz = wz - c[cmd + 2];
         const float dx2 = dx * dx, dy2 = dy * dy;
         r[0] += 1.f;
         r[1] += vx;
@@ -191,39 +202,50 @@ __global__ __launch_bounds__(FLEET_TPB) void fleet_observe_kernel(const duck_fle
       }
     }
     if (!D.standing) {
-      c[5 * nu + 7] = ii;
-      c[5 * nu + 9] = ph0;
-      c[5 * nu + 10] = ph1;
+      c[DUCK_FLEET_CTL_IMITATION_I(nu)] = ii;
+      c[DUCK_FLEET_CTL_IMITATION_PHASE(nu)] = ph0;
+      c[DUCK_FLEET_CTL_IMITATION_PHASE(nu) + 1] = ph1;
     }
   }
 }
 
-// mujoco_infer.py:208-231, one lane per (robot, actuator)
-__global__ __launch_bounds__(FLEET_TPB) void fleet_actuate_kernel(const duck_fleet_desc D, int n,
-                                                                  const float* __restrict__ action, float* ctl,
-                                                                  float* __restrict__ ctrl) {
+// mujoco_infer.py:208-231 for actuator a of robot e: the history shift, the motor target from entry d of the
+// shifted history (0: this period's action), the speed-limit clip, ctl and ctrl. Both actuate kernels are this
+// body, so that with d == 0 the delayed one is the plain one bit for bit.
+__device__ __forceinline__ void fleet_actuate_body(const duck_fleet_desc& D, int n, size_t e, int a, int d,
+                                                   const float* __restrict__ action, float* ctl,
+                                                   float* __restrict__ ctrl) {
 #pragma clang fp contract(off)
-  const int a = threadIdx.x % FLEET_TEAM;
-  const int e0 = blockIdx.x * (FLEET_TPB / FLEET_TEAM) + threadIdx.x / FLEET_TEAM;
   const int nu = D.nu;
-  if (e0 >= n || a >= nu) return;
-  const size_t e = e0;
   float* c = ctl + e * DUCK_FLEET_CTL_SIZE(nu);
-  const float act = action[e * nu + a], last = c[a], last_last = c[nu + a];
-  c[2 * nu + a] = last_last;
-  c[nu + a] = last;
-  c[a] = act;
-  const float scaled = act * D.action_scale;
+  const float act = action[e * nu + a], last = c[DUCK_FLEET_CTL_ACTION(nu, 0) + a],
+              last_last = c[DUCK_FLEET_CTL_ACTION(nu, 1) + a];
+  c[DUCK_FLEET_CTL_ACTION(nu, 2) + a] = last_last;
+  c[DUCK_FLEET_CTL_ACTION(nu, 1) + a] = last;
+  c[DUCK_FLEET_CTL_ACTION(nu, 0) + a] = act;
+  const float used = d == 0 ? act : (d == 1 ? last : last_last);  // entry d of the shifted history
+  const float scaled = used * D.action_scale;
   float mt = D.act_default[a] + scaled;
   if (D.speed_limits) {
-    const float prev = c[4 * nu + a];
+    const float prev = c[DUCK_FLEET_CTL_PREV_MOTOR_TARGETS(nu) + a];
     const float lo = prev - D.target_step, hi = prev + D.target_step;
     mt = mt < lo ? lo : mt;  // np.clip: a NaN target stays NaN
     mt = mt > hi ? hi : mt;
-    c[4 * nu + a] = mt;
+    c[DUCK_FLEET_CTL_PREV_MOTOR_TARGETS(nu) + a] = mt;
   }
-  c[3 * nu + a] = mt;
+  c[DUCK_FLEET_CTL_MOTOR_TARGETS(nu) + a] = mt;
   ctrl[(size_t)a * n + e] = mt;
+}
+
+// one lane per (robot, actuator)
+__global__ __launch_bounds__(FLEET_TPB) void fleet_actuate_kernel(const duck_fleet_desc D, int n,
+                                                                  const float* __restrict__ action, float* ctl,
+                                                                  float* __restrict__ ctrl) {
+  int a;
+  size_t e;
+  const int nu = D.nu;
+  if (!fleet_place(n, a, e) || a >= nu) return;
+  fleet_actuate_body(D, n, e, a, 0, action, ctl, ctrl);
 }
 
 // The loop's disturbances (include/duck_fleet.h: duck_fleet_disturb), the same 16-lane group per robot. Lane l
@@ -242,10 +264,10 @@ __global__ __launch_bounds__(FLEET_TPB) void fleet_disturb_kernel(const duck_fle
                                                                   float* __restrict__ qvel, float* __restrict__ ctl,
                                                                   float* __restrict__ obs) {
 #pragma clang fp contract(off)
-  const int lane = threadIdx.x % FLEET_TEAM;
-  const int e0 = blockIdx.x * (FLEET_TPB / FLEET_TEAM) + threadIdx.x / FLEET_TEAM;
-  if (e0 >= n) return;
-  const size_t e = e0, N = n;
+  int lane;
+  size_t e;
+  if (!fleet_place(n, lane, e)) return;
+  const size_t N = n;
   const int C = DUCK_FLEET_CTL_SIZE(nu), O = DUCK_FLEET_OBS_SIZE(nu);
   const int p = tick[e], t = p + 1;
   Rng r;
@@ -276,7 +298,7 @@ __global__ __launch_bounds__(FLEET_TPB) void fleet_disturb_kernel(const duck_fle
     int id = sched_id[e], seg = t / S.seg_periods;
     id = id < 0 ? 0 : (id > S.n_sched - 1 ? S.n_sched - 1 : id);
     seg = seg < 0 ? 0 : (seg > S.n_seg - 1 ? S.n_seg - 1 : seg);  // (a negative tick reads segment 0, not before the table)
-    ctl[e * C + 5 * nu + lane] = sched[((size_t)id * S.n_seg + seg) * 7 + lane];
+    ctl[e * C + DUCK_FLEET_CTL_COMMAND(nu) + lane] = sched[((size_t)id * S.n_seg + seg) * 7 + lane];
   }
 
   if (lane == 0) {
@@ -309,10 +331,10 @@ __global__ __launch_bounds__(FLEET_TPB) void fleet_record_kernel(
     const uint32_t* __restrict__ qvel, const uint32_t* __restrict__ warm, const uint32_t* __restrict__ aux,
     const uint32_t* __restrict__ ctl, const uint32_t* __restrict__ obs, const uint32_t* __restrict__ action,
     const float* __restrict__ alive, int* head, int* after, uint32_t* __restrict__ ring) {
-  const int lane = threadIdx.x % FLEET_TEAM;
-  const int e0 = blockIdx.x * (FLEET_TPB / FLEET_TEAM) + threadIdx.x / FLEET_TEAM;
-  if (e0 >= n) return;
-  const size_t e = e0, N = n;
+  int lane;
+  size_t e;
+  if (!fleet_place(n, lane, e)) return;
+  const size_t N = n;
   const int h = head[e], af = after[e];
   const bool dead = alive[e] == 0.f;
   if (dead && af > post) return;  // frozen
@@ -374,10 +396,9 @@ __global__ __launch_bounds__(FLEET_TPB) void fleet_sense_delay_kernel(int nu, in
                                                                       const int* __restrict__ lat_tick,
                                                                       const int* __restrict__ lat, uint32_t* line,
                                                                       uint32_t* obs) {
-  const int lane = threadIdx.x % FLEET_TEAM;
-  const int e0 = blockIdx.x * (FLEET_TPB / FLEET_TEAM) + threadIdx.x / FLEET_TEAM;
-  if (e0 >= n || lane >= 6) return;
-  const size_t e = e0;
+  int lane;
+  size_t e;
+  if (!fleet_place(n, lane, e) || lane >= 6) return;
   const int p0 = lat_tick[e];
   const uint32_t p = p0 < 0 ? 0u : (uint32_t)p0;
   const int d = fleet_delay(lat + e * DUCK_FLEET_LAT_SIZE, 1, seed, robot_offset + (long long)e, p);
@@ -398,33 +419,14 @@ __global__ __launch_bounds__(FLEET_TPB) void fleet_actuate_delayed_kernel(const 
                                                                           const int* __restrict__ lat,
                                                                           const float* __restrict__ action,
                                                                           float* ctl, float* __restrict__ ctrl) {
-#pragma clang fp contract(off)
-  const int a = threadIdx.x % FLEET_TEAM;
-  const int e0 = blockIdx.x * (FLEET_TPB / FLEET_TEAM) + threadIdx.x / FLEET_TEAM;
-  const int nu = D.nu;
-  if (e0 >= n) return;
-  const size_t e = e0;
+  int a;
+  size_t e;
+  if (!fleet_place(n, a, e)) return;
   const int p0 = lat_tick[e];
-  if (a >= nu) return;
+  if (a >= D.nu) return;
   const int d = fleet_delay(lat + e * DUCK_FLEET_LAT_SIZE, 0, seed, robot_offset + (long long)e,
                             p0 < 0 ? 0u : (uint32_t)p0);
-  float* c = ctl + e * DUCK_FLEET_CTL_SIZE(nu);
-  const float act = action[e * nu + a], last = c[a], last_last = c[nu + a];
-  c[2 * nu + a] = last_last;
-  c[nu + a] = last;
-  c[a] = act;
-  const float used = d == 0 ? act : (d == 1 ? last : last_last);  // entry d of the shifted history
-  const float scaled = used * D.action_scale;
-  float mt = D.act_default[a] + scaled;
-  if (D.speed_limits) {
-    const float prev = c[4 * nu + a];
-    const float lo = prev - D.target_step, hi = prev + D.target_step;
-    mt = mt < lo ? lo : mt;  // np.clip: a NaN target stays NaN
-    mt = mt > hi ? hi : mt;
-    c[4 * nu + a] = mt;
-  }
-  c[3 * nu + a] = mt;
-  ctrl[(size_t)a * n + e] = mt;
+  fleet_actuate_body(D, n, e, a, d, action, ctl, ctrl);
   if (a == 0) lat_tick[e] = (int)((uint32_t)p0 + 1u);
 }
 
@@ -441,10 +443,9 @@ __global__ __launch_bounds__(FLEET_TPB) void fleet_follow_kernel(int nu, int n, 
                                                                  float* __restrict__ score, uint32_t* __restrict__ ctl,
                                                                  uint32_t* __restrict__ action) {
 #pragma clang fp contract(off)
-  const int lane = threadIdx.x % FLEET_TEAM;
-  const int e0 = blockIdx.x * (FLEET_TPB / FLEET_TEAM) + threadIdx.x / FLEET_TEAM;
-  if (e0 >= n) return;
-  const size_t e = e0;
+  int lane;
+  size_t e;
+  if (!fleet_place(n, lane, e)) return;
   const int O = DUCK_FLEET_OBS_SIZE(nu), W = DUCK_FLEET_LOG_SIZE(nu), C = DUCK_FLEET_CTL_SIZE(nu);
   const int p0 = log_tick[e], p = p0 < 0 ? 0 : p0;
   int id = log_id[e];
@@ -465,7 +466,7 @@ __global__ __launch_bounds__(FLEET_TPB) void fleet_follow_kernel(int nu, int n, 
     }
   }
   if (lane < nu) action[e * nu + lane] = inside ? row[O + lane] : 0u;
-  if (lane < 7 && p < T - 1) ctl[e * C + 5 * nu + lane] = row[W + 6 + lane];
+  if (lane < 7 && p < T - 1) ctl[e * C + DUCK_FLEET_CTL_COMMAND(nu) + lane] = row[W + 6 + lane];
   if (lane == 0) log_tick[e] = inside ? p + 1 : T;
 }
 
@@ -475,6 +476,33 @@ static const char* fleet_desc_error(const duck_fleet_desc* d) {
     if (d->act_qpos[a] < 0 || d->act_qpos[a] >= d->nq || d->act_dof[a] < 0 || d->act_dof[a] >= d->nv)
       return "actuator address outside qpos / qvel";
   return nullptr;
+}
+
+// The checks every fleet entry shares, in their order: the pointers (`null`: one of the entry's is), N's range,
+// `own` (the entry's own complaint about its sizes, or nullptr), the descriptor.
+static int fleet_check(const char* entry, bool null, const duck_fleet_desc* d, int n, const char* own = nullptr) {
+  const char* why = own;
+  if (null || !d) why = "null pointer";
+  else if (n < 0 || n > (1 << 27)) why = "bad size (0 <= N <= 2^27)";
+  else if (!own) why = fleet_desc_error(d);
+  return why ? duck_fail(DUCK_EINVAL, std::string(entry) + ": " + why) : DUCK_OK;
+}
+
+// every sensor row duck_fleet_observe and duck_fleet_record read lies inside the aux record
+static bool fleet_sensors_inside(const duck_fleet_desc* d) {
+  for (int s : {d->gyro, d->accelerometer, d->upvector, d->local_linvel})
+    if (s < 0 || d->sens_off < 0 || (long long)d->sens_off + s + 3 > d->naux) return false;
+  return true;
+}
+
+// a 16-lane group per robot, FLEET_TPB threads a block; N == 0 launches nothing
+template <typename... P, typename... A>
+static int fleet_launch(void (*kernel)(P...), int n, void* stream, A... args) {
+  if (n == 0) return DUCK_OK;
+  const int per = FLEET_TPB / FLEET_TEAM;
+  hipLaunchKernelGGL(kernel, dim3((n + per - 1) / per), dim3(FLEET_TPB), 0, (hipStream_t)stream, args...);
+  HIPCHECK(hipGetLastError());
+  return DUCK_OK;
 }
 }  // namespace
 
@@ -498,134 +526,82 @@ int duck_episode_accumulate(int n, int nmetrics, const float* reward, const floa
 int duck_fleet_observe(const duck_fleet_desc* d, int n, const float* qpos, const float* qvel, const float* aux,
                        float* ctl, float* obs, float* acc, float* alive, void* stream) {
   g_err.clear();
-  if (!d || !qpos || !qvel || !aux || !ctl || !obs || !acc || !alive)
-    return duck_fail(DUCK_EINVAL, "duck_fleet_observe: null pointer");
-  if (n < 0 || n > (1 << 27)) return duck_fail(DUCK_EINVAL, "duck_fleet_observe: bad size (0 <= N <= 2^27)");
-  if (const char* why = fleet_desc_error(d)) return duck_fail(DUCK_EINVAL, std::string("duck_fleet_observe: ") + why);
-  // every aux row the kernel reads lies inside the record
-  const int sensors[4] = {d->gyro, d->accelerometer, d->upvector, d->local_linvel};
-  for (int s : sensors)
-    if (s < 0 || d->sens_off < 0 || (long long)d->sens_off + s + 3 > d->naux)
-      return duck_fail(DUCK_EINVAL, "duck_fleet_observe: sensor address outside the aux record");
+  if (int rc = fleet_check("duck_fleet_observe", !qpos || !qvel || !aux || !ctl || !obs || !acc || !alive, d, n))
+    return rc;
+  if (!fleet_sensors_inside(d))
+    return duck_fail(DUCK_EINVAL, "duck_fleet_observe: sensor address outside the aux record");
   for (int f : d->foot_con)
     if (f < 0 || d->con_off < 0 || (long long)d->con_off + f + 4 > d->naux)
       return duck_fail(DUCK_EINVAL, "duck_fleet_observe: contact slot outside the aux record");
   if (!d->standing && d->nb_steps_in_period < 1)
     return duck_fail(DUCK_EINVAL, "duck_fleet_observe: nb_steps_in_period must be >= 1 unless standing");
-  if (n == 0) return DUCK_OK;
-  const int per = FLEET_TPB / FLEET_TEAM;
-  hipLaunchKernelGGL(fleet_observe_kernel, dim3((n + per - 1) / per), dim3(FLEET_TPB), 0, (hipStream_t)stream, *d, n,
-                     qpos, qvel, aux, ctl, obs, acc, alive);
-  HIPCHECK(hipGetLastError());
-  return DUCK_OK;
+  return fleet_launch(fleet_observe_kernel, n, stream, *d, n, qpos, qvel, aux, ctl, obs, acc, alive);
 }
 
 int duck_fleet_actuate(const duck_fleet_desc* d, int n, const float* action, float* ctl, float* ctrl, void* stream) {
   g_err.clear();
-  if (!d || !action || !ctl || !ctrl) return duck_fail(DUCK_EINVAL, "duck_fleet_actuate: null pointer");
-  if (n < 0 || n > (1 << 27)) return duck_fail(DUCK_EINVAL, "duck_fleet_actuate: bad size (0 <= N <= 2^27)");
-  if (const char* why = fleet_desc_error(d)) return duck_fail(DUCK_EINVAL, std::string("duck_fleet_actuate: ") + why);
-  if (n == 0) return DUCK_OK;
-  const int per = FLEET_TPB / FLEET_TEAM;
-  hipLaunchKernelGGL(fleet_actuate_kernel, dim3((n + per - 1) / per), dim3(FLEET_TPB), 0, (hipStream_t)stream, *d, n,
-                     action, ctl, ctrl);
-  HIPCHECK(hipGetLastError());
-  return DUCK_OK;
+  if (int rc = fleet_check("duck_fleet_actuate", !action || !ctl || !ctrl, d, n)) return rc;
+  return fleet_launch(fleet_actuate_kernel, n, stream, *d, n, action, ctl, ctrl);
 }
 
 int duck_fleet_disturb(const duck_fleet_desc* d, const duck_fleet_disturbance* dis, int n, int64_t robot_offset,
                        int32_t* tick, const float* sched, const int32_t* sched_id, const float* push, float* qvel,
                        float* ctl, float* obs, void* stream) {
   g_err.clear();
+  // (the schedule's complaints come before N's, so the pointers are looked at here)
   if (!d || !dis || !tick || !qvel || !ctl || !obs) return duck_fail(DUCK_EINVAL, "duck_fleet_disturb: null pointer");
   if (sched && !sched_id) return duck_fail(DUCK_EINVAL, "duck_fleet_disturb: a schedule needs sched_id");
   if (sched && (dis->n_sched < 1 || dis->n_seg < 1 || dis->seg_periods < 1))
     return duck_fail(DUCK_EINVAL, "duck_fleet_disturb: a schedule needs n_sched, n_seg, seg_periods >= 1");
-  if (n < 0 || n > (1 << 27)) return duck_fail(DUCK_EINVAL, "duck_fleet_disturb: bad size (0 <= N <= 2^27)");
-  if (const char* why = fleet_desc_error(d)) return duck_fail(DUCK_EINVAL, std::string("duck_fleet_disturb: ") + why);
+  if (int rc = fleet_check("duck_fleet_disturb", false, d, n)) return rc;
   if (push && d->nv < 2) return duck_fail(DUCK_EINVAL, "duck_fleet_disturb: a push table needs nv >= 2");
-  if (n == 0) return DUCK_OK;
   int noisy = 0;
   for (int k = 0; k < DUCK_FLEET_OBS_SIZE(d->nu); k++) noisy |= dis->noise_scale[k] != 0.f;
-  const int per = FLEET_TPB / FLEET_TEAM;
-  hipLaunchKernelGGL(fleet_disturb_kernel, dim3((n + per - 1) / per), dim3(FLEET_TPB), 0, (hipStream_t)stream, *dis,
-                     d->nu, noisy, n, (long long)robot_offset, tick, sched, sched_id, push, qvel, ctl, obs);
-  HIPCHECK(hipGetLastError());
-  return DUCK_OK;
+  return fleet_launch(fleet_disturb_kernel, n, stream, *dis, d->nu, noisy, n, (long long)robot_offset, tick, sched,
+                      sched_id, push, qvel, ctl, obs);
 }
 
 int duck_fleet_record(const duck_fleet_desc* d, int n, int depth, int post, const float* qpos, const float* qvel,
                       const float* warm, const float* aux, const float* ctl, const float* obs, const float* action,
                       const float* alive, int32_t* head, int32_t* after, float* ring, void* stream) {
   g_err.clear();
-  if (!d || !qpos || !qvel || !warm || !aux || !ctl || !obs || !action || !alive || !head || !after || !ring)
-    return duck_fail(DUCK_EINVAL, "duck_fleet_record: null pointer");
-  if (n < 0 || n > (1 << 27)) return duck_fail(DUCK_EINVAL, "duck_fleet_record: bad size (0 <= N <= 2^27)");
-  if (depth < 1 || post < 0) return duck_fail(DUCK_EINVAL, "duck_fleet_record: depth >= 1 and post >= 0");
-  if (const char* why = fleet_desc_error(d)) return duck_fail(DUCK_EINVAL, std::string("duck_fleet_record: ") + why);
-  // every aux row the kernel reads lies inside the record
-  const int sensors[4] = {d->gyro, d->accelerometer, d->upvector, d->local_linvel};
-  for (int s : sensors)
-    if (s < 0 || d->sens_off < 0 || (long long)d->sens_off + s + 3 > d->naux)
-      return duck_fail(DUCK_EINVAL, "duck_fleet_record: sensor address outside the aux record");
+  if (int rc = fleet_check("duck_fleet_record",
+                           !qpos || !qvel || !warm || !aux || !ctl || !obs || !action || !alive || !head || !after || !ring,
+                           d, n, depth < 1 || post < 0 ? "depth >= 1 and post >= 0" : nullptr))
+    return rc;
+  if (!fleet_sensors_inside(d))
+    return duck_fail(DUCK_EINVAL, "duck_fleet_record: sensor address outside the aux record");
   if (4LL * d->nv + d->nu > d->naux)
     return duck_fail(DUCK_EINVAL, "duck_fleet_record: actuator_force rows (4 nv + nu) outside the aux record");
-  if (n == 0) return DUCK_OK;
-  const int per = FLEET_TPB / FLEET_TEAM;
-  hipLaunchKernelGGL(fleet_record_kernel, dim3((n + per - 1) / per), dim3(FLEET_TPB), 0, (hipStream_t)stream, *d, n,
-                     depth, post, (const uint32_t*)qpos, (const uint32_t*)qvel, (const uint32_t*)warm,
-                     (const uint32_t*)aux, (const uint32_t*)ctl, (const uint32_t*)obs, (const uint32_t*)action, alive,
-                     head, after, (uint32_t*)ring);
-  HIPCHECK(hipGetLastError());
-  return DUCK_OK;
+  return fleet_launch(fleet_record_kernel, n, stream, *d, n, depth, post, (const uint32_t*)qpos, (const uint32_t*)qvel,
+                      (const uint32_t*)warm, (const uint32_t*)aux, (const uint32_t*)ctl, (const uint32_t*)obs,
+                      (const uint32_t*)action, alive, head, after, (uint32_t*)ring);
 }
 
 int duck_fleet_sense_delay(const duck_fleet_desc* d, int n, uint64_t seed, int64_t robot_offset, const int32_t* lat_tick,
                            const int32_t* lat, float* line, float* obs, void* stream) {
   g_err.clear();
-  if (!d || !lat_tick || !lat || !line || !obs) return duck_fail(DUCK_EINVAL, "duck_fleet_sense_delay: null pointer");
-  if (n < 0 || n > (1 << 27)) return duck_fail(DUCK_EINVAL, "duck_fleet_sense_delay: bad size (0 <= N <= 2^27)");
-  if (const char* why = fleet_desc_error(d))
-    return duck_fail(DUCK_EINVAL, std::string("duck_fleet_sense_delay: ") + why);
-  if (n == 0) return DUCK_OK;
-  const int per = FLEET_TPB / FLEET_TEAM;
-  hipLaunchKernelGGL(fleet_sense_delay_kernel, dim3((n + per - 1) / per), dim3(FLEET_TPB), 0, (hipStream_t)stream,
-                     d->nu, n, (unsigned long long)seed, (long long)robot_offset, lat_tick, lat, (uint32_t*)line,
-                     (uint32_t*)obs);
-  HIPCHECK(hipGetLastError());
-  return DUCK_OK;
+  if (int rc = fleet_check("duck_fleet_sense_delay", !lat_tick || !lat || !line || !obs, d, n)) return rc;
+  return fleet_launch(fleet_sense_delay_kernel, n, stream, d->nu, n, (unsigned long long)seed, (long long)robot_offset,
+                      lat_tick, lat, (uint32_t*)line, (uint32_t*)obs);
 }
 
 int duck_fleet_actuate_delayed(const duck_fleet_desc* d, int n, uint64_t seed, int64_t robot_offset, int32_t* lat_tick,
                                const int32_t* lat, const float* action, float* ctl, float* ctrl, void* stream) {
   g_err.clear();
-  if (!d || !lat_tick || !lat || !action || !ctl || !ctrl)
-    return duck_fail(DUCK_EINVAL, "duck_fleet_actuate_delayed: null pointer");
-  if (n < 0 || n > (1 << 27)) return duck_fail(DUCK_EINVAL, "duck_fleet_actuate_delayed: bad size (0 <= N <= 2^27)");
-  if (const char* why = fleet_desc_error(d))
-    return duck_fail(DUCK_EINVAL, std::string("duck_fleet_actuate_delayed: ") + why);
-  if (n == 0) return DUCK_OK;
-  const int per = FLEET_TPB / FLEET_TEAM;
-  hipLaunchKernelGGL(fleet_actuate_delayed_kernel, dim3((n + per - 1) / per), dim3(FLEET_TPB), 0, (hipStream_t)stream,
-                     *d, n, (unsigned long long)seed, (long long)robot_offset, lat_tick, lat, action, ctl, ctrl);
-  HIPCHECK(hipGetLastError());
-  return DUCK_OK;
+  if (int rc = fleet_check("duck_fleet_actuate_delayed", !lat_tick || !lat || !action || !ctl || !ctrl, d, n)) return rc;
+  return fleet_launch(fleet_actuate_delayed_kernel, n, stream, *d, n, (unsigned long long)seed, (long long)robot_offset,
+                      lat_tick, lat, action, ctl, ctrl);
 }
 
 int duck_fleet_follow(const duck_fleet_desc* d, int n, int n_log, int T, const float* log, const int32_t* log_id,
                       int32_t* log_tick, const float* obs, float* score, float* ctl, float* action, void* stream) {
   g_err.clear();
-  if (!d || !log || !log_id || !log_tick || !obs || !score || !ctl || !action)
-    return duck_fail(DUCK_EINVAL, "duck_fleet_follow: null pointer");
-  if (n < 0 || n > (1 << 27)) return duck_fail(DUCK_EINVAL, "duck_fleet_follow: bad size (0 <= N <= 2^27)");
-  if (n_log < 1 || T < 1) return duck_fail(DUCK_EINVAL, "duck_fleet_follow: a log needs n_log >= 1 and T >= 1");
-  if (const char* why = fleet_desc_error(d)) return duck_fail(DUCK_EINVAL, std::string("duck_fleet_follow: ") + why);
-  if (n == 0) return DUCK_OK;
-  const int per = FLEET_TPB / FLEET_TEAM;
-  hipLaunchKernelGGL(fleet_follow_kernel, dim3((n + per - 1) / per), dim3(FLEET_TPB), 0, (hipStream_t)stream, d->nu, n,
-                     n_log, T, (const uint32_t*)log, log_id, log_tick, obs, score, (uint32_t*)ctl, (uint32_t*)action);
-  HIPCHECK(hipGetLastError());
-  return DUCK_OK;
+  if (int rc = fleet_check("duck_fleet_follow", !log || !log_id || !log_tick || !obs || !score || !ctl || !action, d, n,
+                           n_log < 1 || T < 1 ? "a log needs n_log >= 1 and T >= 1" : nullptr))
+    return rc;
+  return fleet_launch(fleet_follow_kernel, n, stream, d->nu, n, n_log, T, (const uint32_t*)log, log_id, log_tick, obs,
+                      score, (uint32_t*)ctl, (uint32_t*)action);
 }
 
 uint64_t duck_model_fingerprint(const duck_model_desc* m) {

@@ -195,10 +195,12 @@ def fleet_obs_size(nu: int) -> int:
 
 def ctl_fields(nu: int) -> Dict[str, Tuple[int, int]]:
     """(first column, width) of each field of the per-robot control record (include/duck_fleet.h)."""
-    return {"last_action": (0, nu), "last_last_action": (nu, nu), "last_last_last_action": (2 * nu, nu),
-            "motor_targets": (3 * nu, nu), "prev_motor_targets": (4 * nu, nu), "command": (5 * nu, 7),
-            "imitation_i": (5 * nu + 7, 1), "phase_frequency_factor": (5 * nu + 8, 1),
-            "imitation_phase": (5 * nu + 9, 2)}
+    at = lambda field, *d: HEADERS.value(f"DUCK_FLEET_CTL_{field}({', '.join(str(int(v)) for v in (nu, *d))})")  # noqa: E731
+    return {"last_action": (at("ACTION", 0), nu), "last_last_action": (at("ACTION", 1), nu),
+            "last_last_last_action": (at("ACTION", 2), nu), "motor_targets": (at("MOTOR_TARGETS"), nu),
+            "prev_motor_targets": (at("PREV_MOTOR_TARGETS"), nu), "command": (at("COMMAND"), 7),
+            "imitation_i": (at("IMITATION_I"), 1), "phase_frequency_factor": (at("PHASE_FREQUENCY_FACTOR"), 1),
+            "imitation_phase": (at("IMITATION_PHASE"), 2)}
 
 
 FRAME_SENSORS = ("gyro", "accelerometer", "upvector", "local_linvel")   # the order inside a frame's "sensors"
@@ -456,14 +458,17 @@ class FleetInfer:
                                         None if self.dr is None else self.dr.data_ptr(), int(n_substeps),
                                         self.aux.data_ptr(), self._scratch.data_ptr(), self._stream()), L)
 
-    def observe(self):
-        """duck_fleet_observe on the current state: phase, observation, bookkeeping."""
+    def _launch(self, name: str, *args, lead=()):
+        """A fleet entry of the model's library: the descriptor (then ``lead``) and N in front, tensors as their
+        device pointers (None stays NULL), the stream behind."""
         import ctypes as C
         L = self._lib
-        self._check(L.duck_fleet_observe(C.byref(self.desc), self.num_robots, self.qpos.data_ptr(),
-                                         self.qvel.data_ptr(), self.aux.data_ptr(), self.ctl.data_ptr(),
-                                         self.obs.data_ptr(), self.acc.data_ptr(), self.alive.data_ptr(),
-                                         self._stream()), L)
+        ptrs = [a.data_ptr() if hasattr(a, "data_ptr") else a for a in args]
+        self._check(getattr(L, name)(C.byref(self.desc), *lead, self.num_robots, *ptrs, self._stream()), L)
+
+    def observe(self):
+        """duck_fleet_observe on the current state: phase, observation, bookkeeping."""
+        self._launch("duck_fleet_observe", self.qpos, self.qvel, self.aux, self.ctl, self.obs, self.acc, self.alive)
 
     def policy(self):
         """duck_policy_act on ``obs``."""
@@ -476,10 +481,7 @@ class FleetInfer:
 
     def actuate(self):
         """duck_fleet_actuate: history, motor targets, ctrl."""
-        import ctypes as C
-        L = self._lib
-        self._check(L.duck_fleet_actuate(C.byref(self.desc), self.num_robots, self.action.data_ptr(),
-                                         self.ctl.data_ptr(), self.ctrl.data_ptr(), self._stream()), L)
+        self._launch("duck_fleet_actuate", self.action, self.ctl, self.ctrl)
 
     def act(self):
         """duck_policy_act on ``obs`` (following a log: duck_fleet_follow in its place), then duck_fleet_actuate,
@@ -503,28 +505,17 @@ class FleetInfer:
 
     def follow(self):
         """duck_fleet_follow on this period's ``obs``: the score, the log's action, the next period's command, log_tick."""
-        import ctypes as C
-        L = self._lib
-        self._check(L.duck_fleet_follow(C.byref(self.desc), self.num_robots, int(self.log.shape[0]), int(self.log.shape[1]),
-                                        self.log.data_ptr(), self.log_id.data_ptr(), self.log_tick.data_ptr(),
-                                        self.obs.data_ptr(), self.score.data_ptr(), self.ctl.data_ptr(),
-                                        self.action.data_ptr(), self._stream()), L)
+        self._launch("duck_fleet_follow", int(self.log.shape[0]), int(self.log.shape[1]), self.log, self.log_id,
+                     self.log_tick, self.obs, self.score, self.ctl, self.action)
 
     def sense_delay(self):
         """duck_fleet_sense_delay on this period's ``obs``: the IMU columns into the delay line and, delayed, back."""
-        import ctypes as C
-        L = self._lib
-        self._check(L.duck_fleet_sense_delay(C.byref(self.desc), self.num_robots, self.lat_seed, self.robot_offset,
-                                             self.lat_tick.data_ptr(), self.lat.data_ptr(), self.line.data_ptr(),
-                                             self.obs.data_ptr(), self._stream()), L)
+        self._launch("duck_fleet_sense_delay", self.lat_seed, self.robot_offset, self.lat_tick, self.lat, self.line, self.obs)
 
     def actuate_delayed(self):
         """duck_fleet_actuate_delayed: duck_fleet_actuate on the delayed entry of the history, then lat_tick."""
-        import ctypes as C
-        L = self._lib
-        self._check(L.duck_fleet_actuate_delayed(C.byref(self.desc), self.num_robots, self.lat_seed, self.robot_offset,
-                                                 self.lat_tick.data_ptr(), self.lat.data_ptr(), self.action.data_ptr(),
-                                                 self.ctl.data_ptr(), self.ctrl.data_ptr(), self._stream()), L)
+        self._launch("duck_fleet_actuate_delayed", self.lat_seed, self.robot_offset, self.lat_tick, self.lat, self.action,
+                     self.ctl, self.ctrl)
 
     def disturbed(self) -> bool:
         """Whether a schedule, a push table or a non-zero noise is set (the loop's fifth launch)."""
@@ -533,22 +524,13 @@ class FleetInfer:
     def disturb(self):
         """duck_fleet_disturb on this period's ``obs``: noise, the next period's command and push, the tick."""
         import ctypes as C
-        L = self._lib
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        self._check(L.duck_fleet_disturb(C.byref(self.desc), C.byref(self.dis), self.num_robots, self.robot_offset,
-                                         self.tick.data_ptr(), ptr(self.sched), ptr(self.sched_id), ptr(self.push),
-                                         self.qvel.data_ptr(), self.ctl.data_ptr(), self.obs.data_ptr(),
-                                         self._stream()), L)
+        self._launch("duck_fleet_disturb", self.robot_offset, self.tick, self.sched, self.sched_id, self.push, self.qvel,
+                     self.ctl, self.obs, lead=(C.byref(self.dis),))
 
     def record(self):
         """duck_fleet_record: this period's frame into the ring of every robot not yet frozen."""
-        import ctypes as C
-        L = self._lib
-        self._check(L.duck_fleet_record(C.byref(self.desc), self.num_robots, self.rec_depth, self.rec_post,
-                                        self.qpos.data_ptr(), self.qvel.data_ptr(), self.warm.data_ptr(),
-                                        self.aux.data_ptr(), self.ctl.data_ptr(), self.obs.data_ptr(),
-                                        self.action.data_ptr(), self.alive.data_ptr(), self.rec_head.data_ptr(),
-                                        self.rec_after.data_ptr(), self.ring.data_ptr(), self._stream()), L)
+        self._launch("duck_fleet_record", self.rec_depth, self.rec_post, self.qpos, self.qvel, self.warm, self.aux,
+                     self.ctl, self.obs, self.action, self.alive, self.rec_head, self.rec_after, self.ring)
 
     def _periods(self, k: int, rec: Optional[torch.Tensor] = None, t0: int = 0):
         disturbed, recording = self.disturbed(), self.ring is not None

@@ -9,30 +9,13 @@ tests/mlp_reference.threefry2x32, pinned by known-answer tests. Test infrastruct
 
 import numpy as np
 
-from tests.fleet_reference import ctl_fields
+from tests.fleet_reference import M32, ctl_fields, ctl_size, derive_key, ftz, obs_size
 from tests.mlp_reference import threefry2x32
 
 f32 = np.float32
 KEY_TAG = 0xF1EE      # DUCK_FLEET_KEY_TAG
 PUSH_SIZE = 6         # DUCK_FLEET_PUSH_SIZE
 TEAM = 16             # lanes of a robot's group: the slot assignment pairs columns k and k + 16
-M32 = 0xFFFFFFFF
-
-
-def ftz(x):
-    """float32 with results below the smallest normal flushed to a signed zero."""
-    x = np.asarray(x, dtype=f32)
-    with np.errstate(invalid="ignore"):
-        tiny = np.abs(x) < np.finfo(f32).tiny
-    return np.where(tiny, np.copysign(f32(0), x), x).astype(f32)
-
-
-def derive_key(seed, ids):
-    """csrc/duck_math.h derive_key(seed, id, DUCK_FLEET_KEY_TAG) for int64 global robot ids [N]."""
-    ids = np.asarray(ids, dtype=np.int64).astype(np.uint64)
-    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    hi = (ids >> np.uint64(32)) & np.uint64(M32)
-    return threefry2x32(seed & M32, seed >> 32, ids & np.uint64(M32), np.uint64(KEY_TAG) ^ hi)
 
 
 def noise_slot(k):
@@ -68,10 +51,10 @@ def disturb(nu, seed, noise_scale, robot_offset, tick, qvel, ctl, obs, sched=Non
     place; noise_scale [>= O] float32; sched [S][K][7], sched_id [N], push [N][6] or None.
     Returns {"due" bool [N], "mag", "theta" float32 [N]} of this call's pushes (zeros without a table)."""
     n, O = obs.shape
-    assert O == 17 + 6 * nu and ctl.shape == (n, 5 * nu + 11)
+    assert O == obs_size(nu) and ctl.shape == (n, ctl_size(nu))
     p = tick.astype(np.int64)
     t = p + 1
-    key = derive_key(seed, int(robot_offset) + np.arange(n, dtype=np.int64))
+    key = derive_key(seed, int(robot_offset) + np.arange(n, dtype=np.int64), KEY_TAG)
     scale = np.asarray(noise_scale, dtype=f32)
     for k in range(O):
         if scale[k] != 0:

@@ -9,27 +9,9 @@ kernel's outputs equal these bit for bit. It imports nothing from the package. T
 
 import numpy as np
 
+from tests.fleet_reference import ctl_fields, ctl_size, ftz, log_size, obs_size
+
 f32 = np.float32
-
-
-def obs_size(nu):
-    return 17 + 6 * nu       # DUCK_FLEET_OBS_SIZE
-
-
-def log_size(nu):
-    return 17 + 7 * nu       # DUCK_FLEET_LOG_SIZE
-
-
-def ctl_size(nu):
-    return 5 * nu + 11       # DUCK_FLEET_CTL_SIZE
-
-
-def ftz(x):
-    """float32 with values below the smallest normal flushed to a signed zero."""
-    x = np.asarray(x, dtype=f32)
-    with np.errstate(invalid="ignore"):
-        tiny = np.abs(x) < np.finfo(f32).tiny
-    return np.where(tiny, np.copysign(f32(0), x), x).astype(f32)
 
 
 def follow(nu, log, log_id, log_tick, obs, score, ctl, action):
@@ -61,6 +43,7 @@ def follow(nu, log, log_id, log_tick, obs, score, ctl, action):
     aw[e] = lw[ids[e], p[e], O:]
     # command: row p + 1's, while there is one
     nxt = np.flatnonzero(p + 1 < T)
-    cw[nxt, 5 * nu:5 * nu + 7] = lw[ids[nxt], p[nxt] + 1, 6:13]
+    c0 = ctl_fields(nu)["command"][0]
+    cw[nxt, c0:c0 + 7] = lw[ids[nxt], p[nxt] + 1, 6:13]
     log_tick[:] = np.minimum(p + 1, T).astype(np.int32)
     return p, inside

@@ -10,7 +10,7 @@ pinned by known-answer tests. Test infrastructure only.
 
 import numpy as np
 
-from tests.fleet_reference import ctl_fields
+from tests.fleet_reference import M32, ctl_fields, derive_key
 from tests.mlp_reference import threefry2x32
 
 f32 = np.float32
@@ -18,15 +18,6 @@ LAT_TAG = 0x1A7E      # DUCK_FLEET_LAT_TAG
 MAX_DELAY = 2         # DUCK_FLEET_MAX_DELAY
 LAT_SIZE = 4          # DUCK_FLEET_LAT_SIZE
 SLOTS = MAX_DELAY + 1
-M32 = 0xFFFFFFFF
-
-
-def derive_key(seed, ids, tag=LAT_TAG):
-    """csrc/duck_math.h derive_key(seed, id, tag) for int64 global robot ids [N]."""
-    ids = np.asarray(ids, dtype=np.int64).astype(np.uint64)
-    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    hi = (ids >> np.uint64(32)) & np.uint64(M32)
-    return threefry2x32(seed & M32, seed >> 32, ids & np.uint64(M32), np.uint64(tag) ^ hi)
 
 
 def draw_map(word, lo, hi):

@@ -7,11 +7,9 @@ and the kernel's ring equals this one bit for bit. Test infrastructure only.
 
 import numpy as np
 
+from tests.fleet_reference import frame_size
+
 SENSORS = ("gyro", "accelerometer", "upvector", "local_linvel")
-
-
-def frame_size(nq, nv, nu):
-    return nq + 2 * nv + (5 * nu + 11) + (17 + 6 * nu) + 2 * nu + 12
 
 
 def _words(a):

@@ -1,5 +1,7 @@
 """float32 restatements of the fleet deployment loop's two kernels (include/duck_fleet.h:
-duck_fleet_observe, duck_fleet_actuate) -- mujoco_infer.py:175-197, :67-103 and :208-231 for N robots.
+duck_fleet_observe, duck_fleet_actuate) -- mujoco_infer.py:175-197, :67-103 and :208-231 for N robots -- and
+the tests' one statement of the loop's record sizes and offsets, its flush to zero and its stream keys. The
+header is tested against this module, so it reads neither the header nor the package.
 
 Every value is formed as the header states it: one float32 operation on float32 words, so the kernels'
 outputs equal these bit for bit (the phase's cos / sin excepted: they are compared against float64).
@@ -11,8 +13,11 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
+from tests.mlp_reference import threefry2x32
+
 f32 = np.float32
 TWO_PI = f32(6.2831855)
+M32 = 0xFFFFFFFF
 
 
 def ctl_fields(nu):
@@ -21,6 +26,38 @@ def ctl_fields(nu):
             "motor_targets": (3 * nu, nu), "prev_motor_targets": (4 * nu, nu), "command": (5 * nu, 7),
             "imitation_i": (5 * nu + 7, 1), "phase_frequency_factor": (5 * nu + 8, 1),
             "imitation_phase": (5 * nu + 9, 2)}
+
+
+def ctl_size(nu):
+    return 5 * nu + 11       # DUCK_FLEET_CTL_SIZE
+
+
+def obs_size(nu):
+    return 17 + 6 * nu       # DUCK_FLEET_OBS_SIZE
+
+
+def log_size(nu):
+    return 17 + 7 * nu       # DUCK_FLEET_LOG_SIZE: an obs row, then the action
+
+
+def frame_size(nq, nv, nu):
+    return nq + 2 * nv + ctl_size(nu) + obs_size(nu) + 2 * nu + 12       # DUCK_FLEET_FRAME_SIZE
+
+
+def ftz(x):
+    """float32 with values below the smallest normal flushed to a signed zero, as the library runs."""
+    x = np.asarray(x, dtype=f32)
+    with np.errstate(invalid="ignore"):
+        tiny = np.abs(x) < np.finfo(f32).tiny
+    return np.where(tiny, np.copysign(f32(0), x), x).astype(f32)
+
+
+def derive_key(seed, ids, tag):
+    """csrc/duck_math.h derive_key(seed, id, tag) for int64 global robot ids [N]."""
+    ids = np.asarray(ids, dtype=np.int64).astype(np.uint64)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    hi = (ids >> np.uint64(32)) & np.uint64(M32)
+    return threefry2x32(seed & M32, seed >> 32, ids & np.uint64(M32), np.uint64(tag) ^ hi)
 
 
 def desc_values(d):

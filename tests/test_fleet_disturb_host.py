@@ -13,6 +13,8 @@ import pytest
 
 from open_duck_playground_amd import native, sim2sim
 from tests import fleet_disturb_reference as D
+from tests import fleet_reference as R
+from tests.fleet_helpers import host_desc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
@@ -29,17 +31,9 @@ def test_symbol_is_declared_listed_and_exported():
     assert int(re.search(r"#define DUCK_FLEET_KEY_TAG 0x([0-9A-Fa-f]+)u", hdr).group(1), 16) == D.KEY_TAG
 
 
-def _desc():
-    d = native.DuckFleetDesc()
-    d.nq, d.nv, d.nu, d.naux = 21, 20, 14, 200
-    for a in range(14):
-        d.act_qpos[a], d.act_dof[a] = 7 + a, 6 + a
-    return d
-
-
 def test_refusals_come_before_any_launch():
     L = native.lib()
-    d, s = _desc(), native.DuckFleetDisturbance()
+    d, s = host_desc(), native.DuckFleetDisturbance()
     one = C.c_void_p(16)   # (never dereferenced: every call below is refused before any launch)
     D_, S_ = C.byref(d), C.byref(s)
 
@@ -67,14 +61,14 @@ def test_refusals_come_before_any_launch():
     for a in range(14):
         d.act_dof[a] = 0
     assert call(push=one) == -1 and b"nv >= 2" in L.duck_last_error()
-    d = _desc()
+    d = host_desc()
     assert L.duck_fleet_disturb(C.byref(d), S_, 0, 0, one, None, None, one, one, one, one, None) == 0   # an empty fleet
 
 
 # --- the restatement on hand-written rows ---------------------------------------------------
 def _blank(n, nu=3, nv=12):
-    return (np.zeros(n, np.int32), np.zeros((nv, n), f32), np.zeros((n, 5 * nu + 11), f32),
-            np.zeros((n, 17 + 6 * nu), f32))
+    return (np.zeros(n, np.int32), np.zeros((nv, n), f32), np.zeros((n, R.ctl_size(nu)), f32),
+            np.zeros((n, R.obs_size(nu)), f32))
 
 
 def test_push_is_due_at_first_and_every_interval():
@@ -87,7 +81,7 @@ def test_push_is_due_at_first_and_every_interval():
                      [1, 1, 0.25, 0.25, 0.0, 0.0]], f32)   # before every period from 1 on
     when = [[] for _ in range(n)]
     for call in range(12):
-        out = D.disturb(nu, 5, np.zeros(17 + 6 * nu, f32), 0, tick, qvel, ctl, obs, push=push)
+        out = D.disturb(nu, 5, np.zeros(R.obs_size(nu), f32), 0, tick, qvel, ctl, obs, push=push)
         for e in np.flatnonzero(out["due"]):
             when[e].append(call + 1)      # the call of period p = call decides period t = call + 1
     assert when == [[3, 7, 11], [3], [], list(range(1, 13))]
@@ -100,7 +94,7 @@ def test_push_ranges_and_direction():
     n, nu = 64, 3
     tick, qvel, ctl, obs = _blank(n, nu)
     push = np.tile(np.array([1, 0, 0.1, 1.0, -1.0, 2.0], f32), (n, 1))
-    out = D.disturb(nu, 9, np.zeros(17 + 6 * nu, f32), 0, tick, qvel, ctl, obs, push=push)
+    out = D.disturb(nu, 9, np.zeros(R.obs_size(nu), f32), 0, tick, qvel, ctl, obs, push=push)
     assert out["due"].all() and (out["mag"] >= f32(0.1)).all() and (out["mag"] <= f32(1.0)).all()
     assert (out["theta"] >= -1).all() and (out["theta"] <= 2).all() and len(set(out["mag"])) > 32
     np.testing.assert_allclose(np.hypot(qvel[0], qvel[1]), out["mag"], rtol=1e-6)
@@ -113,10 +107,10 @@ def test_last_segment_is_held_and_ids_are_clamped():
     tick, qvel, ctl, obs = _blank(n, nu)
     sched = np.arange(2 * 3 * 7, dtype=f32).reshape(2, 3, 7)
     ids = np.array([0, 1, 7], np.int32)         # 7 is clamped to the last schedule
-    c0 = 5 * nu
+    c0 = R.ctl_fields(nu)["command"][0]
     seen = []
     for call in range(9):
-        D.disturb(nu, 0, np.zeros(17 + 6 * nu, f32), 0, tick, qvel, ctl, obs, sched=sched, sched_id=ids, seg_periods=2)
+        D.disturb(nu, 0, np.zeros(R.obs_size(nu), f32), 0, tick, qvel, ctl, obs, sched=sched, sched_id=ids, seg_periods=2)
         seen.append(int(ctl[0, c0]) // 7)       # the segment robot 0's command of period call + 1 comes from
         assert ctl[1, c0:c0 + 7].tobytes() == ctl[2, c0:c0 + 7].tobytes()
         assert ctl[1, c0] == ctl[0, c0] + 21
@@ -126,7 +120,7 @@ def test_last_segment_is_held_and_ids_are_clamped():
 
 def test_noise_bounds_zero_scale_and_independence():
     n, nu = 40, 3
-    O = 17 + 6 * nu
+    O = R.obs_size(nu)
     tick, qvel, ctl, obs = _blank(n, nu)
     scale = np.zeros(O, f32)
     scale[[0, 5, 16, 17, 33, O - 1]] = [0.1, 0.05, 0.03, 2.5, 1.0, 0.5]
@@ -170,11 +164,11 @@ def test_slots_pair_columns_sixteen_apart():
 
 
 def test_key_is_the_global_robot_id():
-    a = D.derive_key(3, [0, 1, 2 ** 32 + 1])
-    b = D.derive_key(3, [1])
+    a = D.derive_key(3, [0, 1, 2 ** 32 + 1], D.KEY_TAG)
+    b = D.derive_key(3, [1], D.KEY_TAG)
     assert a[0][1] == b[0][0] and a[1][1] == b[1][0]
     assert (a[0][2], a[1][2]) != (a[0][1], a[1][1])              # the id's high word counts
-    assert D.derive_key(4, [1])[0][0] != b[0][0]
+    assert D.derive_key(4, [1], D.KEY_TAG)[0][0] != b[0][0]
 
 
 # --- push_report ------------------------------------------------------------------------------

@@ -12,14 +12,12 @@ import pytest
 
 from open_duck_playground_amd import cabi, native, sim2sim
 from tests import fleet_follow_reference as F
+from tests import fleet_reference as R
+from tests.fleet_helpers import f32_bits as bits, host_desc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 NAN_PAYLOAD, NEG_ZERO = np.int32(0x7FC12345), np.int32(-0x80000000)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=f32).view(np.int32)
 
 
 # --- the C ABI --------------------------------------------------------------------------
@@ -39,17 +37,9 @@ def test_symbol_and_constants():
     assert "policy or follow, actuate or actuate_delayed, [record]" in hdr
 
 
-def _desc():
-    d = native.DuckFleetDesc()
-    d.nq, d.nv, d.nu, d.naux = 21, 20, 14, 200
-    for a in range(14):
-        d.act_qpos[a], d.act_dof[a] = 7 + a, 6 + a
-    return d
-
-
 def test_refusals_come_before_any_launch():
     L = native.lib()
-    d = _desc()
+    d = host_desc()
     one = C.c_void_p(16)   # (never dereferenced: every call below is refused before any launch)
 
     def call(desc=C.byref(d), n=1, n_log=1, T=1, null=None):
@@ -115,10 +105,11 @@ def test_actions_and_commands_are_copied_and_the_end_is_held():
     np.testing.assert_array_equal(bits(b["action"][:2]), bits(np.tile(b["log"][0, 0, O:], (2, 1))))
     np.testing.assert_array_equal(bits(b["action"][2]), bits(b["log"][0, 1, O:]))
     assert b["action"].view(np.int32)[0, 0] == NAN_PAYLOAD and b["action"].view(np.int32)[2, 1] == NEG_ZERO
-    cmd = slice(5 * nu, 5 * nu + 7)
+    c0 = R.ctl_fields(nu)["command"][0]
+    cmd = slice(c0, c0 + 7)
     np.testing.assert_array_equal(bits(b["ctl"][:2, cmd]), bits(np.tile(b["log"][0, 1, 6:13], (2, 1))))   # row p + 1's
     np.testing.assert_array_equal(bits(b["ctl"][2, cmd]), bits(b["log"][0, 2, 6:13]))
-    assert b["ctl"].view(np.int32)[0, 5 * nu] == NEG_ZERO
+    assert b["ctl"].view(np.int32)[0, c0] == NEG_ZERO
     keep = np.ones(b["ctl"].shape[1], bool)
     keep[cmd] = False
     np.testing.assert_array_equal(bits(b["ctl"][:, keep]), bits(ctl0[:, keep]))                           # nothing else of ctl
@@ -138,13 +129,13 @@ def test_actions_and_commands_are_copied_and_the_end_is_held():
 def test_the_log_id_is_clamped():
     nu, n, n_log = 2, 5, 3
     b = _buffers(n, nu, n_log, 2, seed=2)
-    O = F.obs_size(nu)
+    O, c0 = F.obs_size(nu), R.ctl_fields(nu)["command"][0]
     ids = np.array([-7, 0, 1, 2, 9], np.int32)
     tick = np.zeros(n, np.int32)
     F.follow(nu, b["log"], ids, tick, b["obs"], b["score"], b["ctl"], b["action"])
     for e, want in enumerate([0, 0, 1, 2, 2]):
         np.testing.assert_array_equal(b["action"][e], b["log"][want, 0, O:])
-        np.testing.assert_array_equal(b["ctl"][e, 5 * nu:5 * nu + 7], b["log"][want, 1, 6:13])
+        np.testing.assert_array_equal(b["ctl"][e, c0:c0 + 7], b["log"][want, 1, 6:13])
     assert list(ids) == [-7, 0, 1, 2, 9]
 
 

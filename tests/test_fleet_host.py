@@ -206,9 +206,32 @@ def test_descriptor_comes_from_the_model():
     assert ctl_fields(m.nu) == R.ctl_fields(m.nu)
 
 
+@pytest.mark.parametrize("nu", [1, 3, 14, 16])
+def test_offset_macros_are_the_control_record(nu):
+    """The header's offset macros against the tests' own statement of the record, field by field; the fields
+    tile [0, DUCK_FLEET_CTL_SIZE(nu)); sim2sim.ctl_fields is the same mapping."""
+    from open_duck_playground_amd.cabi import HEADERS
+    from open_duck_playground_amd.sim2sim import ctl_fields
+    macros = {"last_action": f"ACTION({nu}, 0)", "last_last_action": f"ACTION({nu}, 1)",
+              "last_last_last_action": f"ACTION({nu}, 2)", "motor_targets": f"MOTOR_TARGETS({nu})",
+              "prev_motor_targets": f"PREV_MOTOR_TARGETS({nu})", "command": f"COMMAND({nu})",
+              "imitation_i": f"IMITATION_I({nu})", "phase_frequency_factor": f"PHASE_FREQUENCY_FACTOR({nu})",
+              "imitation_phase": f"IMITATION_PHASE({nu})"}
+    want = R.ctl_fields(nu)
+    assert set(macros) == set(want)
+    for name, (first, _) in want.items():
+        assert HEADERS.value("DUCK_FLEET_CTL_" + macros[name]) == first, name
+    end = 0
+    for first, width in sorted(want.values()):      # no gap, no overlap
+        assert first == end and width >= 1
+        end = first + width
+    assert end == HEADERS.value(f"DUCK_FLEET_CTL_SIZE({nu})") == R.ctl_size(nu)
+    assert ctl_fields(nu) == want
+
+
 # --- the restatements on hand-written rows ----------------------------------------------
 def _blank(d, n):
-    C = 5 * d.nu + 11
+    C = R.ctl_size(d.nu)
     z = lambda k: np.zeros((k, n), f32)  # noqa: E731
     ctl = np.zeros((n, C), f32)
     ctl[:, R.ctl_fields(d.nu)["phase_frequency_factor"][0]] = 1.0
@@ -251,7 +274,7 @@ def test_reference_contacts():
     aux[left + 1, 3] = np.nan
     np.testing.assert_array_equal(R.contacts(d, aux), [[1, 0], [0, 0], [0, 0], [0, 0]])
     obs, _ = R.observe(d, qpos, qvel, aux, ctl, torch.zeros(4, 6), torch.ones(4))
-    O = 17 + 6 * d.nu
+    O = R.obs_size(d.nu)
     np.testing.assert_array_equal(obs[:, O - 4:O - 2], [[1, 0], [0, 0], [0, 0], [0, 0]])
 
 

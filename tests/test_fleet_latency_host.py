@@ -14,6 +14,7 @@ from open_duck_playground_amd import cabi, native, sim2sim
 from tests import fleet_disturb_reference as D
 from tests import fleet_latency_reference as T
 from tests import fleet_reference as R
+from tests.fleet_helpers import host_desc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
@@ -39,17 +40,9 @@ def test_symbols_and_constants():
     assert act[1][2] is C.c_uint64 and act[1][3] is C.c_int64 and len(act[1]) == 10
 
 
-def _desc():
-    d = native.DuckFleetDesc()
-    d.nq, d.nv, d.nu, d.naux = 21, 20, 14, 200
-    for a in range(14):
-        d.act_qpos[a], d.act_dof[a] = 7 + a, 6 + a
-    return d
-
-
 def test_refusals_come_before_any_launch():
     L = native.lib()
-    d = _desc()
+    d = host_desc()
     one = C.c_void_p(16)   # (never dereferenced: every call below is refused before any launch)
     for name, nptr in (("duck_fleet_sense_delay", 4), ("duck_fleet_actuate_delayed", 5)):
         f = getattr(L, name)
@@ -134,7 +127,7 @@ def test_zero_delay_is_the_plain_actuate():
     nu, n = 3, 6
     d = R.make_desc(nu=nu)
     rng = np.random.default_rng(2)
-    ctl_a = rng.normal(size=(n, 5 * nu + 11)).astype(f32)
+    ctl_a = rng.normal(size=(n, R.ctl_size(nu))).astype(f32)
     ctl_b = ctl_a.copy()
     tick = np.zeros(n, np.int32)
     lat = np.zeros((n, 4), np.int32)
@@ -149,7 +142,7 @@ def test_zero_delay_is_the_plain_actuate():
 def test_fixed_action_delay_takes_the_older_entry():
     nu, n = 2, 3
     d = R.make_desc(nu=nu, speed_limits=0)
-    ctl = np.zeros((n, 5 * nu + 11), f32)
+    ctl = np.zeros((n, R.ctl_size(nu)), f32)
     tick = np.zeros(n, np.int32)
     lat = np.array([[0, 0, 0, 0], [1, 1, 0, 0], [2, 2, 0, 0]], np.int32)
     default = np.asarray(d.act_default[:nu], f32)
@@ -166,7 +159,7 @@ def test_fixed_action_delay_takes_the_older_entry():
 
 
 def test_delay_line_fills_wraps_and_keeps_bits():
-    n, O = 4, 17 + 6 * 3
+    n, O = 4, R.obs_size(3)
     line, tick = np.zeros((n, 3, 6), f32), np.zeros(n, np.int32)
     lat = np.array([[0, 0, 0, 0], [0, 0, 1, 1], [0, 0, 2, 2], [2, 2, 0, 2]], np.int32)
     seen = []

@@ -47,14 +47,10 @@ def test_frame_fields_partition_the_frame(nq, nv, nu):
 
 
 # --- the restatement of the rule ------------------------------------------------------------------
-def _desc(nu=3):
-    return R.make_desc(nu=nu)
-
-
 def _inputs(d, n, rng):
     z = lambda *s: rng.normal(size=s).astype(f32)  # noqa: E731
-    return dict(qpos=z(d.nq, n), qvel=z(d.nv, n), warm=z(d.nv, n), aux=z(d.naux, n), ctl=z(n, 5 * d.nu + 11),
-                obs=z(n, 17 + 6 * d.nu), action=z(n, d.nu))
+    return dict(qpos=z(d.nq, n), qvel=z(d.nv, n), warm=z(d.nv, n), aux=z(d.naux, n), ctl=z(n, R.ctl_size(d.nu)),
+                obs=z(n, R.obs_size(d.nu)), action=z(n, d.nu))
 
 
 def _run(d, n, depth, post, calls, dies_at, seed=0):
@@ -76,7 +72,7 @@ def _run(d, n, depth, post, calls, dies_at, seed=0):
 
 
 def test_a_robot_alive_throughout_holds_the_last_depth_calls():
-    d, depth = _desc(), 4
+    d, depth = R.make_desc(), 4
     calls = 2 * depth + 3                                   # wraps twice
     ring, head, after, seen, _ = _run(d, 2, depth, 1, calls, np.zeros(2, int))
     assert list(head) == [calls, calls] and list(after) == [0, 0]
@@ -89,7 +85,7 @@ def test_a_robot_alive_throughout_holds_the_last_depth_calls():
 
 @pytest.mark.parametrize("post", [0, 2])
 def test_a_robot_dying_at_call_c_holds_up_to_c_plus_post_and_is_frozen(post):
-    d, depth, calls = _desc(), 5, 12
+    d, depth, calls = R.make_desc(), 5, 12
     dies = np.array([0, 3, 7, 4])                           # robot 0 lives; 1 dies before the ring wraps; 2 after it has
     ring, head, after, seen, rings = _run(d, 4, depth, post, calls, dies)
     for e, c in enumerate(dies):
@@ -109,7 +105,7 @@ def test_a_robot_dying_at_call_c_holds_up_to_c_plus_post_and_is_frozen(post):
 
 @pytest.mark.parametrize("post", [0, 1, 3])
 def test_a_robot_dead_from_the_first_call_writes_post_plus_one_frames(post):
-    d, depth = _desc(), 6
+    d, depth = R.make_desc(), 6
     ring, head, after, seen, _ = _run(d, 2, depth, post, 9, np.array([1, 0]))
     assert head[0] == post + 1 and after[0] == post + 1 and head[1] == 9
     frames, period = sim2sim.unroll_ring(ring[0], head[0], depth)
@@ -119,7 +115,7 @@ def test_a_robot_dead_from_the_first_call_writes_post_plus_one_frames(post):
 
 
 def test_depth_one_holds_the_last_written_frame():
-    d = _desc()
+    d = R.make_desc()
     ring, head, after, seen, _ = _run(d, 3, 1, 1, 7, np.array([0, 3, 1]))
     np.testing.assert_array_equal(ring[0, 0], seen[6, 0])       # alive: call 7
     np.testing.assert_array_equal(ring[1, 0], seen[3, 1])       # died at 3, post 1: call 4
@@ -131,7 +127,7 @@ def test_depth_one_holds_the_last_written_frame():
 
 
 def test_frames_keep_their_bits():
-    d = _desc()
+    d = R.make_desc()
     rng = np.random.default_rng(5)
     x = _inputs(d, 2, rng)
     for a in x.values():

@@ -13,50 +13,16 @@ import numpy as np
 import pytest
 import torch
 
-from open_duck_playground_amd import native, onnx_export, ppo
+from open_duck_playground_amd import native
 from open_duck_playground_amd.onnx_infer import OnnxGraph, dense_policy
 from open_duck_playground_amd.sim2sim import FleetInfer, MjInfer
 from tests import fleet_reference as R
+from tests.fleet_helpers import c_desc, commands, dev, f32_bits as bits, net_and_policy_file, stream  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 PHASE_TOL = 2e-6   # three float32 roundings on an angle below 2 pi (about 1.1e-6) + 2 ulp of cosf / sinf
-
-
-def bits(a):
-    return np.ascontiguousarray(np.asarray(a, dtype=f32)).view(np.int32)
-
-
-def c_desc(d):
-    D = native.DuckFleetDesc()
-    for name, _ in D._fields_:
-        v = getattr(d, name)
-        if isinstance(v, list):
-            for k, x in enumerate(v):
-                getattr(D, name)[k] = x
-        else:
-            setattr(D, name, v)
-    return D
-
-
-def dev(a, gpu):
-    return torch.tensor(np.ascontiguousarray(a, dtype=f32), device=gpu)
-
-
-def stream(gpu):
-    return C.c_void_p(torch.cuda.current_stream(torch.device(gpu)).cuda_stream)
-
-
-@pytest.fixture(scope="module")
-def policy_file(tmp_path_factory):
-    torch.manual_seed(3)
-    net = ppo.ActorCritic(101, 212, 14, ppo.PPOConfig())
-    rng = np.random.default_rng(0)
-    net.obs_norm.update(torch.tensor(rng.normal(0.0, 1.0, size=(500, 101)), dtype=torch.float32))
-    path = str(tmp_path_factory.mktemp("onnx") / "policy.onnx")
-    onnx_export.export_onnx(net, 14, 101, output_path=path)
-    return net, path
 
 
 # --- the kernels alone --------------------------------------------------------------------
@@ -84,8 +50,8 @@ def test_observe_kernel_alone(gpu, n, nu, standing):
     D = c_desc(d)
     rng = np.random.default_rng(100 + n + nu)
     F = R.ctl_fields(nu)
-    O = 17 + 6 * nu
-    ctl = rng.normal(size=(n, 5 * nu + 11)).astype(f32)
+    O = R.obs_size(nu)
+    ctl = rng.normal(size=(n, R.ctl_size(nu))).astype(f32)
     ctl[:, F["imitation_i"][0]] = rng.uniform(0, 40, n).astype(f32)
     ctl[:, F["phase_frequency_factor"][0]] = rng.uniform(0.5, 1.5, n).astype(f32)
     if n > 2:
@@ -133,7 +99,7 @@ def test_actuate_kernel_alone(gpu, n, nu, limits):
     D = c_desc(d)
     rng = np.random.default_rng(200 + n + nu)
     F = R.ctl_fields(nu)
-    ctl = rng.normal(size=(n, 5 * nu + 11)).astype(f32)
+    ctl = rng.normal(size=(n, R.ctl_size(nu))).astype(f32)
     default = np.asarray(d.act_default[:nu], f32)
     p = F["prev_motor_targets"][0]
     ctl_d = dev(ctl, gpu)
@@ -165,17 +131,10 @@ def test_actuate_kernel_alone(gpu, n, nu, limits):
 
 
 # --- the loop ------------------------------------------------------------------------------
-def _commands(n, seed=11):
-    rng = np.random.default_rng(seed)
-    c = np.zeros((n, 7), f32)
-    c[:, 0], c[:, 1], c[:, 2] = rng.uniform(-0.15, 0.15, n), rng.uniform(-0.2, 0.2, n), rng.uniform(-1, 1, n)
-    return c
-
-
 @pytest.mark.parametrize("randomize", [None, 7])
 def test_batch_invariance(policy_file, gpu, randomize):
     _, path = policy_file
-    cmd = _commands(33)
+    cmd = commands(33)
     big = FleetInfer("flat_terrain", path, 33, device=gpu, randomize=randomize)
     one = FleetInfer("flat_terrain", path, 1, device=gpu, randomize=randomize)
     if randomize is not None:   # duck_randomize is keyed by the global robot id: robot 20's record, copied
@@ -196,7 +155,7 @@ def test_batch_invariance(policy_file, gpu, randomize):
 def test_graph_replay_equals_eager(policy_file, gpu, monkeypatch):
     _, path = policy_file
     monkeypatch.setattr(FleetInfer, "CHUNK", 4)
-    cmd = _commands(8, seed=12)
+    cmd = commands(8, seed=12)
     a = FleetInfer("flat_terrain", path, 8, device=gpu)
     b = FleetInfer("flat_terrain", path, 8, device=gpu)
     a.set_commands(cmd)

@@ -13,61 +13,16 @@ import numpy as np
 import pytest
 import torch
 
-from open_duck_playground_amd import native, onnx_export, ppo
+from open_duck_playground_amd import native
 from open_duck_playground_amd.sim2sim import FleetInfer
 from tests import fleet_disturb_reference as D
 from tests import fleet_reference as R
+from tests.fleet_helpers import bits, c_desc, c_dis, commands, dev, policy_file, stream  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 PUSH_TOL = 2.0 ** -22     # x mag: 2 ulp of the accurate cosf / sinf (|.| <= 1) plus the product's rounding
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.int32) if a.dtype == np.float32 else a
-
-
-def c_desc(d):
-    out = native.DuckFleetDesc()
-    for name, _ in out._fields_:
-        v = getattr(d, name)
-        if isinstance(v, list):
-            for k, x in enumerate(v):
-                getattr(out, name)[k] = x
-        else:
-            setattr(out, name, v)
-    return out
-
-
-def c_dis(seed, scale, sched=None, seg_periods=1):
-    s = native.DuckFleetDisturbance()
-    s.seed = seed
-    for k, v in enumerate(scale):
-        s.noise_scale[k] = float(v)
-    if sched is not None:
-        s.n_sched, s.n_seg, s.seg_periods = sched.shape[0], sched.shape[1], seg_periods
-    return s
-
-
-def dev(a, gpu):
-    return torch.tensor(np.ascontiguousarray(a), device=gpu)
-
-
-def stream(gpu):
-    return C.c_void_p(torch.cuda.current_stream(torch.device(gpu)).cuda_stream)
-
-
-@pytest.fixture(scope="module")
-def policy_file(tmp_path_factory):
-    torch.manual_seed(3)
-    net = ppo.ActorCritic(101, 212, 14, ppo.PPOConfig())
-    rng = np.random.default_rng(0)
-    net.obs_norm.update(torch.tensor(rng.normal(0.0, 1.0, size=(500, 101)), dtype=torch.float32))
-    path = str(tmp_path_factory.mktemp("onnx") / "policy.onnx")
-    onnx_export.export_onnx(net, 14, 101, output_path=path)
-    return path
 
 
 # --- the kernel alone -----------------------------------------------------------------------
@@ -95,7 +50,7 @@ def test_disturb_kernel_alone(gpu, n, nu, offset):
     d = R.make_desc(nu=nu)
     Dc = c_desc(d)
     rng = np.random.default_rng(300 + n + nu)
-    O, Cw = 17 + 6 * nu, 5 * nu + 11
+    O, Cw = R.obs_size(nu), R.ctl_size(nu)
     scale = np.where(rng.random(O) < 0.5, rng.uniform(0.01, 2.0, O), 0.0).astype(f32)
     scale[0], scale[1], scale[O - 1] = 0.1, 0.0, 0.5         # first and last column noisy, column 1 not
     sched = rng.normal(size=(3, 3, 7)).astype(f32)
@@ -153,7 +108,7 @@ def test_a_robot_is_its_global_id(gpu):
     d = R.make_desc(nu=nu)
     Dc = c_desc(d)
     rng = np.random.default_rng(7)
-    O, Cw = 17 + 6 * nu, 5 * nu + 11
+    O, Cw = R.obs_size(nu), R.ctl_size(nu)
     scale = rng.uniform(0.01, 1.0, O).astype(f32)
     sched = rng.normal(size=(2, 2, 7)).astype(f32)
     S = c_dis(5, scale, sched, seg_periods=2)
@@ -182,15 +137,8 @@ def test_a_robot_is_its_global_id(gpu):
 
 
 # --- the loop --------------------------------------------------------------------------------
-def _commands(n, seed=11):
-    rng = np.random.default_rng(seed)
-    c = np.zeros((n, 7), f32)
-    c[:, 0], c[:, 1], c[:, 2] = rng.uniform(-0.15, 0.15, n), rng.uniform(-0.2, 0.2, n), rng.uniform(-1, 1, n)
-    return c
-
-
 def _all_three(fleet, n):
-    table = _commands(2 * 4, seed=21).reshape(2, 4, 7)
+    table = commands(2 * 4, seed=21).reshape(2, 4, 7)
     fleet.set_command_schedule(table, np.arange(n) % 2, 3)
     fleet.set_pushes(5, 4, (0.1, 0.5), (0.0, 6.0))
     fleet.set_noise(1.0, seed=3)
@@ -220,7 +168,7 @@ def test_graph_replay_equals_eager_disturbed(policy_file, gpu, monkeypatch):
 
 def test_push_is_a_velocity_edit_before_the_periods_physics(policy_file, gpu):
     mag = f32(0.3)
-    cmd = _commands(4, seed=13)
+    cmd = commands(4, seed=13)
     a = FleetInfer("flat_terrain", policy_file, 4, device=gpu, pushes=(3, 0, float(mag), 0.0))
     b = FleetInfer("flat_terrain", policy_file, 4, device=gpu)
     a.set_commands(cmd)
@@ -242,7 +190,7 @@ def test_push_is_a_velocity_edit_before_the_periods_physics(policy_file, gpu):
 
 
 def test_off_means_off(policy_file, gpu, monkeypatch):
-    cmd = _commands(6, seed=14)
+    cmd = commands(6, seed=14)
     a = FleetInfer("flat_terrain", policy_file, 6, device=gpu)
     b = FleetInfer("flat_terrain", policy_file, 6, device=gpu)
     a.set_commands(cmd)
@@ -270,7 +218,7 @@ def test_off_means_off(policy_file, gpu, monkeypatch):
 
 
 def test_noise_reaches_the_policy_and_not_the_bookkeeping(policy_file, gpu):
-    cmd = _commands(5, seed=15)
+    cmd = commands(5, seed=15)
     a = FleetInfer("flat_terrain", policy_file, 5, device=gpu)
     b = FleetInfer("flat_terrain", policy_file, 5, device=gpu, noise=(1.0, 8))
     a.set_commands(cmd)
@@ -294,7 +242,7 @@ def test_setters_validate_and_drop_the_graph_when_they_must(policy_file, gpu, mo
     monkeypatch.setattr(FleetInfer, "CHUNK", 2)
     n = 4
     f = FleetInfer("flat_terrain", policy_file, n, device=gpu)
-    table = _commands(6, seed=22).reshape(2, 3, 7)
+    table = commands(6, seed=22).reshape(2, 3, 7)
     bad = [lambda: f.set_command_schedule(table, [0, 1, 2, 0], 2),            # id out of range
            lambda: f.set_command_schedule(table, [0, 1, 0], 2),               # shape
            lambda: f.set_command_schedule(table[:, :, :6], None, 2),
@@ -315,14 +263,14 @@ def test_setters_validate_and_drop_the_graph_when_they_must(policy_file, gpu, mo
     g = f.graph
     assert g is not None
     f.set_pushes(3, 0, 0.2, 1.0)                      # same buffers: the graph reads the new rows
-    f.set_command_schedule(_commands(8, seed=23).reshape(2, 4, 7), np.arange(n) % 2, 3)
+    f.set_command_schedule(commands(8, seed=23).reshape(2, 4, 7), np.arange(n) % 2, 3)
     f.set_noise(1.0, seed=3)                          # nothing changed
     assert f.graph is g
     f.set_noise(1.0, seed=4)                          # the seed is passed by value
     assert f.graph is None
     f.run(2)
     assert f.graph is not None
-    f.set_command_schedule(_commands(8, seed=23).reshape(2, 4, 7), np.arange(n) % 2, 5)   # so is seg_periods
+    f.set_command_schedule(commands(8, seed=23).reshape(2, 4, 7), np.arange(n) % 2, 5)   # so is seg_periods
     assert f.graph is None
     f.run(2)
     f.set_pushes(None)                                # a disturbance switched off

@@ -10,10 +10,11 @@ import numpy as np
 import pytest
 import torch
 
-from open_duck_playground_amd import native, onnx_export, ppo, sim2sim
+from open_duck_playground_amd import native, sim2sim
 from open_duck_playground_amd.sim2sim import FleetInfer
 from tests import fleet_follow_reference as F
 from tests import fleet_reference as R
+from tests.fleet_helpers import bits, c_desc, commands, guarded, guards_hold, policy_file, stream  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -22,50 +23,6 @@ NAN_PAYLOAD, NEG_ZERO = np.int32(0x7FC12345), np.int32(-0x80000000)
 SEED = 7              # the randomisation seed of the self-consistency tests
 ROBOT = 20            # ... and the robot whose model made the log
 PERIODS = 12          # rows of the shared log (13 recorded periods)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.int32) if a.dtype == np.float32 else a
-
-
-def c_desc(d):
-    out = native.DuckFleetDesc()
-    for name, _ in out._fields_:
-        v = getattr(d, name)
-        if isinstance(v, list):
-            for k, x in enumerate(v):
-                getattr(out, name)[k] = x
-        else:
-            setattr(out, name, v)
-    return out
-
-
-def stream(gpu):
-    return C.c_void_p(torch.cuda.current_stream(torch.device(gpu)).cuda_stream)
-
-
-def guarded(a, gpu):
-    """``a`` on the device with a guard row before and after it: (the whole tensor, the view of ``a``)."""
-    g = np.full((1,) + a.shape[1:], 7, a.dtype)
-    t = torch.tensor(np.concatenate([g, a, g]), device=gpu)
-    return t, t[1:-1]
-
-
-def guards_hold(t):
-    t = t.cpu().numpy()
-    return bool((t[0] == 7).all() and (t[-1] == 7).all())
-
-
-@pytest.fixture(scope="module")
-def policy_file(tmp_path_factory):
-    torch.manual_seed(3)
-    net = ppo.ActorCritic(101, 212, 14, ppo.PPOConfig())
-    rng = np.random.default_rng(0)
-    net.obs_norm.update(torch.tensor(rng.normal(0.0, 1.0, size=(500, 101)), dtype=torch.float32))
-    path = str(tmp_path_factory.mktemp("onnx") / "policy.onnx")
-    onnx_export.export_onnx(net, 14, 101, output_path=path)
-    return path
 
 
 # --- the kernel alone -----------------------------------------------------------------------
@@ -159,17 +116,11 @@ def test_follow_arguments(gpu):
     native.check(call(), L)
     torch.cuda.synchronize()
     assert (tick == 1).all() and (score == 1).all() and (action == 2).all()
-    assert (ctl[:, 5 * nu:5 * nu + 7] == 2).all() and (ctl[:, :5 * nu] == 0).all() and (ctl[:, 5 * nu + 7:] == 0).all()
+    c0 = R.ctl_fields(nu)["command"][0]
+    assert (ctl[:, c0:c0 + 7] == 2).all() and (ctl[:, :c0] == 0).all() and (ctl[:, c0 + 7:] == 0).all()
 
 
 # --- the loop --------------------------------------------------------------------------------
-def _commands(n, seed=11):
-    rng = np.random.default_rng(seed)
-    c = np.zeros((n, 7), f32)
-    c[:, 0], c[:, 1], c[:, 2] = rng.uniform(-0.15, 0.15, n), rng.uniform(-0.2, 0.2, n), rng.uniform(-1, 1, n)
-    return c
-
-
 @pytest.fixture(scope="module")
 def closed_loop(policy_file, gpu):
     """One closed-loop robot with the test policy on the model of robot ROBOT of duck_randomize(SEED), the command
@@ -178,7 +129,7 @@ def closed_loop(policy_file, gpu):
     one = FleetInfer("flat_terrain", policy_file, 1, device=gpu, randomize=0, robot_offset=ROBOT, recorder=(PERIODS + 1, 0))
     one.dr.copy_(src.dr.view(-1, 33)[:, ROBOT])
     one.restart()                                   # the loop's first substep runs on the randomised model
-    cmd = _commands(2, seed=35)
+    cmd = commands(2, seed=35)
     one.set_commands(cmd[0])
     a = one.run(6, record=True)
     one.set_commands(cmd[1])
@@ -237,7 +188,7 @@ def test_a_delay_grid_finds_the_logs_delays(policy_file, gpu):
     """A log made under an action delay of 1 and an IMU delay of 2, followed by the 3 x 3 delay grid on the same
     nominal model: the cell (1, 2) scores exactly 0, every other cell more."""
     made = FleetInfer("flat_terrain", policy_file, 1, device=gpu, latency=(1, 2, 5))
-    made.set_commands(_commands(1, seed=36)[0])
+    made.set_commands(commands(1, seed=36)[0])
     log = sim2sim.log_from_saved_obs(made.run(PERIODS + 1, record=True)[:, 0])
     cells = sim2sim.delay_grid("3x3")
     fleet = FleetInfer("flat_terrain", None, len(cells), device=gpu, follow=(log, None),
@@ -299,7 +250,7 @@ def test_a_robot_is_its_global_id_while_following(closed_loop, gpu):
 
 def test_set_log_none_leaves_the_plain_loop(closed_loop, policy_file, gpu, monkeypatch):
     n, periods = 5, 6
-    cmd = _commands(n, seed=37)
+    cmd = commands(n, seed=37)
     a = FleetInfer("flat_terrain", policy_file, n, device=gpu, randomize=SEED, follow=(closed_loop["log"], None))
     a.run(3)
     assert a.following() and (a.log_tick == 3).all()

@@ -14,51 +14,16 @@ import numpy as np
 import pytest
 import torch
 
-from open_duck_playground_amd import native, onnx_export, ppo
+from open_duck_playground_amd import native
 from open_duck_playground_amd.sim2sim import FRAME_SENSORS, FleetInfer, aux_fields, frame_fields
 from tests import fleet_record_reference as K
 from tests import fleet_reference as R
+from tests.fleet_helpers import bits, c_desc, commands, dev, policy_file, stream  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 SENTINEL = np.int32(0x7FC0BEEF)       # a NaN with a payload that no input below holds
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.int32) if a.dtype == np.float32 else a
-
-
-def c_desc(d):
-    out = native.DuckFleetDesc()
-    for name, _ in out._fields_:
-        v = getattr(d, name)
-        if isinstance(v, list):
-            for k, x in enumerate(v):
-                getattr(out, name)[k] = x
-        else:
-            setattr(out, name, v)
-    return out
-
-
-def dev(a, gpu):
-    return torch.tensor(np.ascontiguousarray(a), device=gpu)
-
-
-def stream(gpu):
-    return C.c_void_p(torch.cuda.current_stream(torch.device(gpu)).cuda_stream)
-
-
-@pytest.fixture(scope="module")
-def policy_file(tmp_path_factory):
-    torch.manual_seed(3)
-    net = ppo.ActorCritic(101, 212, 14, ppo.PPOConfig())
-    rng = np.random.default_rng(0)
-    net.obs_norm.update(torch.tensor(rng.normal(0.0, 1.0, size=(500, 101)), dtype=torch.float32))
-    path = str(tmp_path_factory.mktemp("onnx") / "policy.onnx")
-    onnx_export.export_onnx(net, 14, 101, output_path=path)
-    return path
 
 
 # --- the kernel alone -----------------------------------------------------------------------
@@ -76,7 +41,7 @@ SPECIAL = np.array([0x7FC12345, 0x7F800001, -0x00345678, -0x80000000, 0x00000001
 def _inputs(d, n, rng):
     out = {}
     for name, shape in (("qpos", (d.nq, n)), ("qvel", (d.nv, n)), ("warm", (d.nv, n)), ("aux", (d.naux, n)),
-                        ("ctl", (n, 5 * d.nu + 11)), ("obs", (n, 17 + 6 * d.nu)), ("action", (n, d.nu))):
+                        ("ctl", (n, R.ctl_size(d.nu))), ("obs", (n, R.obs_size(d.nu))), ("action", (n, d.nu))):
         a = rng.normal(size=shape).astype(f32)
         pick = rng.integers(0, 4 * len(SPECIAL), size=shape)
         w = a.view(np.int32)
@@ -191,16 +156,9 @@ def test_record_arguments(gpu):
 
 
 # --- the loop --------------------------------------------------------------------------------
-def _commands(n, seed=11):
-    rng = np.random.default_rng(seed)
-    c = np.zeros((n, 7), f32)
-    c[:, 0], c[:, 1], c[:, 2] = rng.uniform(-0.15, 0.15, n), rng.uniform(-0.2, 0.2, n), rng.uniform(-1, 1, n)
-    return c
-
-
 def _disturbed_fleet(path, n, gpu, **kw):
     """DR, a 3-segment schedule, drawn pushes first at period 2 and every 3 after, noise at level 1."""
-    table = _commands(2 * 3, seed=21).reshape(2, 3, 7)
+    table = commands(2 * 3, seed=21).reshape(2, 3, 7)
     return FleetInfer("flat_terrain", path, n, device=gpu, randomize=7, command_schedule=(table, np.arange(n) % 2, 5),
                       pushes=(2, 3, (0.1, 0.5), (0.0, 6.0)), noise=(1.0, 3), **kw)
 
@@ -255,7 +213,7 @@ def test_frames_are_the_truth(policy_file, gpu):
     5..10; robot 1 (fell in period 1) 1..2; robot 3 (fell in period 5) 1..6; robot 5 (fell in period 7: the fall
     frame and one more) 3..8."""
     fleet = FleetInfer("flat_terrain", policy_file, 6, device=gpu, recorder=(6, 1))
-    fleet.set_commands(_commands(6, seed=31))
+    fleet.set_commands(commands(6, seed=31))
     m = fleet.model
     q = fleet.state()[0]
     q[1] = _flipped(q[1])
@@ -343,7 +301,7 @@ def test_replay_reproduces_the_recorded_periods(policy_file, gpu):
 
 def test_replay_of_an_undisturbed_fleet(policy_file, gpu):
     fleet = FleetInfer("flat_terrain", policy_file, 3, device=gpu, recorder=(6, 0))
-    fleet.set_commands(_commands(3, seed=32))
+    fleet.set_commands(commands(3, seed=32))
     assert not fleet.disturbed() and fleet.dr is None
     fleet.run(6)
     _assert_replay(fleet, 2)

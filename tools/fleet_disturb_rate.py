@@ -19,13 +19,8 @@ again after them (another process places its buffers and code elsewhere, and the
 of a microsecond with it), and the undisturbed period is checked against the [min, max] those runs report.
 """
 
-import argparse
 import os
-import re
-import statistics
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 import torch
@@ -34,72 +29,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from open_duck_playground_amd import native, onnx_export, ppo  # noqa: E402
+from open_duck_playground_amd import native  # noqa: E402
 from open_duck_playground_amd.sim2sim import FleetInfer, command_grid, resample_schedule  # noqa: E402
-
-
-def capture(fleet, body):
-    fleet.restart()
-    body()                                   # eager once: code objects loaded before the capture
-    torch.cuda.synchronize(fleet.device)
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        body()
-    return g
-
-
-def replay_seconds(fleet, g, reps: int) -> float:
-    fleet.restart()
-    g.replay()                               # the warm-up chunk
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        g.replay()
-    e1.record()
-    torch.cuda.synchronize(fleet.device)
-    return e0.elapsed_time(e1) * 1e-3 / reps
-
-
-def spread(v):
-    return statistics.median(v), min(v), max(v)
-
-
-def parent_periods(root: str, sizes: str, chunk: int, reps: int, repeat: int, device: str):
-    """{N: (median, min, max) period us} of the parent checkout's tools/fleet_rate.py, and its output."""
-    r = subprocess.run([sys.executable, os.path.join(root, "tools", "fleet_rate.py"), "--sizes", sizes, "--chunk",
-                        str(chunk), "--reps", str(reps), "--repeat", str(repeat), "--device", device], cwd=root,
-                       capture_output=True, text=True, timeout=900)
-    if r.returncode != 0:
-        raise SystemExit(f"the parent's fleet_rate.py failed:\n{r.stdout}\n{r.stderr}")
-    out = {}
-    for m in re.finditer(r"^\s*(\d+)\s+[\d,]+\s+[\d,.]+\s+([\d.]+) \[([\d.]+), ([\d.]+)\]", r.stdout, re.M):
-        out[int(m.group(1))] = tuple(float(m.group(k)) for k in (2, 3, 4))
-    return out, r.stdout
+from tools.fleet_rate_common import (Report, capture, export_policy, parent_periods, parent_run,  # noqa: E402, F401
+                                     parent_verdict, parse, parser, replay_seconds, spread)
 
 
 def main() -> int:
-    p = argparse.ArgumentParser()
-    p.add_argument("--out", default=None)
-    p.add_argument("--chunk", type=int, default=50)
-    p.add_argument("--reps", type=int, default=10)
-    p.add_argument("--repeat", type=int, default=3)
-    p.add_argument("--sizes", default="1,1024,4096")
-    p.add_argument("--parent_root", default=None)
-    p.add_argument("--device", default="cuda:0")
-    args = p.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("fleet_disturb_rate.py measures on the GPU; none is available")
-    lines = []
-
-    def say(s=""):
-        print(s, flush=True)
-        lines.append(s)
-
-    torch.manual_seed(3)
-    net = ppo.ActorCritic(101, 212, 14, ppo.PPOConfig())
-    net.obs_norm.update(torch.tensor(np.random.default_rng(0).normal(size=(500, 101)), dtype=torch.float32))
-    path = os.path.join(tempfile.mkdtemp(), "policy.onnx")
-    onnx_export.export_onnx(net, 14, 101, output_path=path)
+    args = parse("fleet_disturb_rate.py", parser())
+    say, path = Report(), export_policy()
     chunk, reps, rep = args.chunk, args.reps, args.repeat
     say(f"fleet_disturb_rate: flat_terrain, {torch.cuda.get_device_name(0)}, build {native.lib().duck_build_id().decode()[:12]}")
     say(f"graphs of {chunk} control periods, {reps} replays timed with HIP events after a warm-up replay, "
@@ -111,7 +49,7 @@ def main() -> int:
     cells = command_grid("3x3x3")
     undisturbed, runs = {}, []
     if args.parent_root:
-        runs.append(parent_periods(os.path.abspath(args.parent_root), args.sizes, chunk, reps, rep, args.device))
+        runs.append(parent_run(args))
     for n in [int(v) for v in args.sizes.split(",")]:
         plain = FleetInfer("flat_terrain", path, n, device=args.device)
         plain.set_commands(cells[np.arange(n) % len(cells)])
@@ -144,25 +82,9 @@ def main() -> int:
         say(f"{n:>7} {fmt(und):>24} {fmt(par):>24} {fmt(dis):>24} {alo[0]:>17.1f} {dis[0] - und[0]:>+9.1f}")
         del plain, dist, graphs
     if args.parent_root:
-        runs.append(parent_periods(os.path.abspath(args.parent_root), args.sizes, chunk, reps, rep, args.device))
-        say()
-        say("the parent commit's tools/fleet_rate.py, run in its own checkout as a child process of this job, once "
-            "before the graphs above and once after them:")
-        for k, (_, text) in enumerate(runs):
-            for line in text.rstrip().splitlines():
-                say(f"  {('before', 'after')[k]} | " + line)
-        say()
-        for n in sorted(undisturbed):
-            u = undisturbed[n]
-            each = ", ".join(f"[{r[n][1]:.1f}, {r[n][2]:.1f}]" for r, _ in runs)
-            lo, hi = min(r[n][1] for r, _ in runs), max(r[n][2] for r, _ in runs)
-            verdict = "inside" if lo <= u[0] <= hi else ("below (faster than)" if u[0] < lo else "ABOVE (slower than)")
-            say(f"undisturbed period at {n} robots: {u[0]:.1f} us [{u[1]:.1f}, {u[2]:.1f}]; the parent's two runs {each}: "
-                f"{verdict} the parent's [{lo:.1f}, {hi:.1f}]")
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+        runs.append(parent_run(args))
+        parent_verdict(say, runs, undisturbed, "undisturbed period", widened=False)
+    say.write(args.out)
     return 0
 
 

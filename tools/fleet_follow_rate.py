@@ -20,10 +20,8 @@ process before this commit's graphs and again after them, and the period with no
 [min, max] those two runs report, widened by the difference between the two runs' medians.
 """
 
-import argparse
 import os
 import sys
-import tempfile
 
 import numpy as np
 import torch
@@ -32,34 +30,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from open_duck_playground_amd import native, onnx_export, ppo  # noqa: E402
+from open_duck_playground_amd import native  # noqa: E402
 from open_duck_playground_amd.sim2sim import FleetInfer, command_grid, log_from_saved_obs  # noqa: E402
-from tools.fleet_disturb_rate import capture, parent_periods, replay_seconds, spread  # noqa: E402
+from tools.fleet_rate_common import (Report, capture, export_policy, parent_run, parent_verdict, parse,  # noqa: E402
+                                     parser, replay_seconds, spread)
 
 
 def main() -> int:
-    p = argparse.ArgumentParser()
-    p.add_argument("--out", default=None)
-    p.add_argument("--chunk", type=int, default=50)
-    p.add_argument("--reps", type=int, default=10)
-    p.add_argument("--repeat", type=int, default=3)
-    p.add_argument("--sizes", default="1,1024,4096")
-    p.add_argument("--parent_root", default=None)
-    p.add_argument("--device", default="cuda:0")
-    args = p.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("fleet_follow_rate.py measures on the GPU; none is available")
-    lines = []
-
-    def say(s=""):
-        print(s, flush=True)
-        lines.append(s)
-
-    torch.manual_seed(3)
-    net = ppo.ActorCritic(101, 212, 14, ppo.PPOConfig())
-    net.obs_norm.update(torch.tensor(np.random.default_rng(0).normal(size=(500, 101)), dtype=torch.float32))
-    path = os.path.join(tempfile.mkdtemp(), "policy.onnx")
-    onnx_export.export_onnx(net, 14, 101, output_path=path)
+    args = parse("fleet_follow_rate.py", parser())
+    say, path = Report(), export_policy()
     chunk, reps, rep = args.chunk, args.reps, args.repeat
     rows = chunk * (reps + 2)          # the eager body before a capture or the warm-up replay, then the timed replays
     say(f"fleet_follow_rate: flat_terrain, {torch.cuda.get_device_name(0)}, build {native.lib().duck_build_id().decode()[:12]}")
@@ -76,7 +55,7 @@ def main() -> int:
     say(f"{'robots':>7} {'policy us':>22} {'following us':>22} {'added us':>9} {'policy alone us':>16} {'follow alone us':>16}")
     no_log, runs = {}, []
     if args.parent_root:
-        runs.append(parent_periods(os.path.abspath(args.parent_root), args.sizes, chunk, reps, rep, args.device))
+        runs.append(parent_run(args))
     for n in [int(v) for v in args.sizes.split(",")]:
         plain = FleetInfer("flat_terrain", path, n, device=args.device)
         plain.set_commands(cells[np.arange(n) % len(cells)])
@@ -102,26 +81,9 @@ def main() -> int:
         say(f"{n:>7} {fmt(pol):>22} {fmt(fol):>22} {fol[0] - pol[0]:>+9.1f} {p_alone[0]:>16.1f} {f_alone[0]:>16.1f}")
         del plain, foll, graphs
     if args.parent_root:
-        runs.append(parent_periods(os.path.abspath(args.parent_root), args.sizes, chunk, reps, rep, args.device))
-        say()
-        say("the parent commit's tools/fleet_rate.py, run in its own checkout as a child process of this job, once "
-            "before the graphs above and once after them:")
-        for k, (_, text) in enumerate(runs):
-            for line in text.rstrip().splitlines():
-                say(f"  {('before', 'after')[k]} | " + line)
-        say()
-        for n in sorted(no_log):
-            u = no_log[n]
-            each = ", ".join(f"{r[n][0]:.1f} [{r[n][1]:.1f}, {r[n][2]:.1f}]" for r, _ in runs)
-            widen = abs(runs[0][0][n][0] - runs[1][0][n][0])
-            lo, hi = min(r[n][1] for r, _ in runs) - widen, max(r[n][2] for r, _ in runs) + widen
-            verdict = "inside" if lo <= u[0] <= hi else ("below (faster than)" if u[0] < lo else "ABOVE (slower than)")
-            say(f"period with no log set at {n} robots: {u[0]:.1f} us [{u[1]:.1f}, {u[2]:.1f}]; the parent's two runs "
-                f"{each}, their medians {widen:.1f} us apart: {verdict} the parent's widened [{lo:.1f}, {hi:.1f}]")
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+        runs.append(parent_run(args))
+        parent_verdict(say, runs, no_log, "period with no log set")
+    say.write(args.out)
     return 0
 
 

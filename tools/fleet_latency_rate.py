@@ -25,10 +25,8 @@ process before this commit's graphs and again after them, and the period with th
 against the [min, max] those two runs report, widened by the difference between the two runs' medians.
 """
 
-import argparse
 import os
 import sys
-import tempfile
 
 import numpy as np
 import torch
@@ -37,34 +35,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from open_duck_playground_amd import native, onnx_export, ppo  # noqa: E402
+from open_duck_playground_amd import native  # noqa: E402
 from open_duck_playground_amd.sim2sim import FleetInfer, command_grid  # noqa: E402
-from tools.fleet_disturb_rate import capture, parent_periods, replay_seconds, spread  # noqa: E402
+from tools.fleet_rate_common import (Report, capture, export_policy, parent_run, parent_verdict, parse,  # noqa: E402
+                                     parser, replay_seconds, spread)
 
 
 def main() -> int:
-    p = argparse.ArgumentParser()
-    p.add_argument("--out", default=None)
-    p.add_argument("--chunk", type=int, default=50)
-    p.add_argument("--reps", type=int, default=10)
-    p.add_argument("--repeat", type=int, default=3)
-    p.add_argument("--sizes", default="1,1024,4096")
-    p.add_argument("--parent_root", default=None)
-    p.add_argument("--device", default="cuda:0")
-    args = p.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("fleet_latency_rate.py measures on the GPU; none is available")
-    lines = []
-
-    def say(s=""):
-        print(s, flush=True)
-        lines.append(s)
-
-    torch.manual_seed(3)
-    net = ppo.ActorCritic(101, 212, 14, ppo.PPOConfig())
-    net.obs_norm.update(torch.tensor(np.random.default_rng(0).normal(size=(500, 101)), dtype=torch.float32))
-    path = os.path.join(tempfile.mkdtemp(), "policy.onnx")
-    onnx_export.export_onnx(net, 14, 101, output_path=path)
+    args = parse("fleet_latency_rate.py", parser())
+    say, path = Report(), export_policy()
     chunk, reps, rep = args.chunk, args.reps, args.repeat
     say(f"fleet_latency_rate: flat_terrain, {torch.cuda.get_device_name(0)}, build {native.lib().duck_build_id().decode()[:12]}")
     say(f"graphs of {chunk} control periods, {reps} replays timed with HIP events after a warm-up replay, "
@@ -77,7 +56,7 @@ def main() -> int:
     cells = command_grid("3x3x3")
     off_period, runs = {}, []
     if args.parent_root:
-        runs.append(parent_periods(os.path.abspath(args.parent_root), args.sizes, chunk, reps, rep, args.device))
+        runs.append(parent_run(args))
     for n in [int(v) for v in args.sizes.split(",")]:
         def fleet(action, sense):
             f = FleetInfer("flat_terrain", path, n, device=args.device)
@@ -116,26 +95,9 @@ def main() -> int:
             f"{a_alone[0]:>17.1f} {d_alone[0]:>17.1f} {s_alone[0]:>15.1f}")
         del fleets, plain, both, graphs
     if args.parent_root:
-        runs.append(parent_periods(os.path.abspath(args.parent_root), args.sizes, chunk, reps, rep, args.device))
-        say()
-        say("the parent commit's tools/fleet_rate.py, run in its own checkout as a child process of this job, once "
-            "before the graphs above and once after them:")
-        for k, (_, text) in enumerate(runs):
-            for line in text.rstrip().splitlines():
-                say(f"  {('before', 'after')[k]} | " + line)
-        say()
-        for n in sorted(off_period):
-            u = off_period[n]
-            each = ", ".join(f"{r[n][0]:.1f} [{r[n][1]:.1f}, {r[n][2]:.1f}]" for r, _ in runs)
-            widen = abs(runs[0][0][n][0] - runs[1][0][n][0])
-            lo, hi = min(r[n][1] for r, _ in runs) - widen, max(r[n][2] for r, _ in runs) + widen
-            verdict = "inside" if lo <= u[0] <= hi else ("below (faster than)" if u[0] < lo else "ABOVE (slower than)")
-            say(f"period with the latency off at {n} robots: {u[0]:.1f} us [{u[1]:.1f}, {u[2]:.1f}]; the parent's two runs "
-                f"{each}, their medians {widen:.1f} us apart: {verdict} the parent's widened [{lo:.1f}, {hi:.1f}]")
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+        runs.append(parent_run(args))
+        parent_verdict(say, runs, off_period, "period with the latency off")
+    say.write(args.out)
     return 0
 
 

@@ -13,22 +13,20 @@ untrained ActorCritic(101, 212, 14) exported to ONNX: the rates do not depend on
 trajectories (and so the contact work of the physics) do.
 """
 
-import argparse
 import os
 import statistics
 import sys
-import tempfile
 import time
 
-import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from open_duck_playground_amd import native, onnx_export, ppo  # noqa: E402
+from open_duck_playground_amd import native  # noqa: E402
 from open_duck_playground_amd.sim2sim import FleetInfer, MjInfer  # noqa: E402
+from tools.fleet_rate_common import Report, export_policy, parse, parser  # noqa: E402
 
 
 def graph_seconds(fleet, body, reps: int, repeat: int):
@@ -54,28 +52,8 @@ def graph_seconds(fleet, body, reps: int, repeat: int):
 
 
 def main() -> int:
-    p = argparse.ArgumentParser()
-    p.add_argument("--out", default=None)
-    p.add_argument("--chunk", type=int, default=50)
-    p.add_argument("--reps", type=int, default=10)
-    p.add_argument("--repeat", type=int, default=3)
-    p.add_argument("--sizes", default="1,1024,4096")
-    p.add_argument("--device", default="cuda:0")
-    args = p.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("fleet_rate.py measures on the GPU; none is available")
-    lines = []
-
-    def say(s=""):
-        print(s, flush=True)
-        lines.append(s)
-
-    torch.manual_seed(3)
-    net = ppo.ActorCritic(101, 212, 14, ppo.PPOConfig())
-    net.obs_norm.update(torch.tensor(np.random.default_rng(0).normal(size=(500, 101)), dtype=torch.float32))
-    tmp = tempfile.mkdtemp()
-    path = os.path.join(tmp, "policy.onnx")
-    onnx_export.export_onnx(net, 14, 101, output_path=path)
+    args = parse("fleet_rate.py", parser(parent_root=False))
+    say, path = Report(), export_policy()
     chunk, reps, rep = args.chunk, args.reps, args.repeat
     say(f"fleet_rate: flat_terrain, {torch.cuda.get_device_name(0)}, build {native.lib().duck_build_id().decode()[:12]}")
     say(f"graphs of {chunk} control periods, {reps} replays timed with HIP events after a warm-up replay, "
@@ -125,10 +103,7 @@ def main() -> int:
                 f"{again[2] / chunk * 1e6:.1f}], without {b:.1f} us [{lean[1] / chunk * 1e6:.1f}, {lean[2] / chunk * 1e6:.1f}]: "
                 f"the record costs {100 * (a - b) / b:+.1f} % of the launch, {100 * (a - b) / us[0]:+.1f} % of the period")
         del fleet
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    say.write(args.out)
     return 0
 
 
