@@ -15,6 +15,7 @@
 #pragma once
 #include <utility>
 
+#include "duck_ldlpairs.h"
 #include "duck_mcols.h"
 #include "duck_physics.h"
 
@@ -22,6 +23,7 @@ constexpr int TEAM = 16;
 constexpr int TEAM_WG = 16;  // envs (teams) per workgroup: 256 threads = 4 waves
 constexpr int TPB = TEAM * TEAM_WG;  // the block size of every env kernel
 typedef __attribute__((address_space(3))) int lds_int;
+typedef float f2v __attribute__((ext_vector_type(2)));
 typedef float f4v __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) f4v lds_f4;
 
@@ -1119,6 +1121,7 @@ struct TPhys {
   using MCo = MCols<Md, TEAM>;
   static constexpr bool MCOLS_LEAN = LAT == 0 && mcols_lean<Md>();
   static constexpr bool zrow(int r, int s) { return MCOLS_LEAN && MCo::zero_row(r, s); }
+  using LP2 = LdlPairs<Md, TEAM>;
   struct Fac {
     float col[NC][NV];
     float dg[NC];
@@ -1141,12 +1144,30 @@ struct TPhys {
       fac_mult<K, Md::dof_parentid[I]>(F, inv, t);
     }
   }
+  // Ancestor rows 2m, 2m + 1 of K inside a set's range take their two updates as one packed FMA
+  // (duck_ldlpairs.h; done at row 2m, row 2m + 1 then has no code): (t_2m, t_2m+1), the two rows and a
+  // splat of H[K][c], each half the fused multiply-add of the scalar form, so the factor's bits are the
+  // scalar code's (flat: a factorization's 131 updates are 57 packed and 17 scalar FMAs). The columns stay
+  // scalars everywhere else, and the pair is put together here: with the columns held as pairs (and these
+  // updates still scalar FMAs) flat + backlash's qacc_smooth moved by ulps in dofs 17-19, so some product
+  // elsewhere contracted differently once its operand came out of a vector (profiles/r12_packed_ab.txt).
+  // (Built with vector-combine off, native.py: the pass turns the two adjacent column reads into one vector
+  // load of the stack object before it is promoted to registers, and the object then stays in scratch.)
   template <int K, int I>
   static DK void fac_upd(Fac& F, const float* t) {
     if constexpr (I >= 0) {
-#pragma unroll
-      for (int s = 0; s < NC; s++)
-        if (TEAM * s <= I) F.col[s][I] -= t[I] * F.col[s][K];
+      static_for<0, NC>([&](auto ss) {
+        constexpr int S = decltype(ss)::value;
+        if constexpr (LP2::lo(K, I, S)) {
+          const f2v tp = {t[I], t[I + 1]}, ck = {F.col[S][K], F.col[S][K]};
+          f2v c = {F.col[S][I], F.col[S][I + 1]};
+          c -= tp * ck;
+          F.col[S][I] = c.x;
+          F.col[S][I + 1] = c.y;
+        } else if constexpr (TEAM * S <= I && !LP2::hi(K, I, S)) {
+          F.col[S][I] -= t[I] * F.col[S][K];
+        }
+      });
       fac_upd<K, Md::dof_parentid[I]>(F, t);
     }
   }

@@ -44,6 +44,14 @@ class DuckError(RuntimeError):
 # the rough + backlash physics_kernel compute a wrong Newton step.
 ILP_FLAGS = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 
+# the scene units (variant_*.hip) only. No vector-combine: the LDL' row updates put two adjacent column
+# registers into one packed FMA (duck_team.h fac_upd); that pass turns the two scalar reads into a vector load
+# of the columns' stack object before it is promoted to registers, which then stays in scratch (flat step
+# kernel: 168 scratch instructions, private segment 288 -> 384 bytes). Without the pass: none and 288 bytes,
+# and the pass did nothing else in these units (the parent's rough + backlash unit compiles to the same
+# assembly with and without it). The learner's GEMM unit changes with the flag and does not get it.
+SCENE_FLAGS = ["-mllvm", "-disable-vector-combine"]
+
 
 def _base_flags(inc: str) -> list:
     # fp32 division and sqrt as v_rcp/v_sqrt (1-2 ulp) instead of the correctly rounded
@@ -59,7 +67,7 @@ def _base_flags(inc: str) -> list:
 
 def compile_flags() -> list:
     """The hipcc flags of the shipped scene units (tools: occupancy_probe.sh, ISA studies)."""
-    return _base_flags(os.path.join(CSRC, "generated")) + ILP_FLAGS
+    return _base_flags(os.path.join(CSRC, "generated")) + ILP_FLAGS + SCENE_FLAGS
 
 
 def build(verbose: bool = False, defines=(), out: str = None, extra_flags=(), no_ilp=(), isa_check: bool = True,
@@ -106,7 +114,7 @@ def _build_unlocked(verbose, defines, out, extra_flags, no_ilp, isa_check, gen_d
     ilp = ILP_FLAGS
     # build id: sha1 of every source, header and flag that shapes the code (duck_build_id()); the
     # .so itself is not byte-reproducible (object paths), so profiles are keyed by this instead
-    h = hashlib.sha1(" ".join(flags + ilp + sorted(no_ilp)).encode())
+    h = hashlib.sha1(" ".join(flags + ilp + SCENE_FLAGS + sorted(no_ilp)).encode())
     for d in sorted(set(deps) - {os.path.abspath(__file__)}):
         h.update(os.path.relpath(d, ROOT).encode())
         h.update(open(d, "rb").read())
@@ -115,7 +123,8 @@ def _build_unlocked(verbose, defines, out, extra_flags, no_ilp, isa_check, gen_d
         objs, procs = [], []
         for src in srcs:
             obj = os.path.join(tmp, os.path.basename(src) + ".o")
-            cmd = ["hipcc"] + flags + ([] if os.path.basename(src) in no_ilp else ilp) + ["-c", "-o", obj, src]
+            cmd = ["hipcc"] + flags + ([] if os.path.basename(src) in no_ilp else ilp) + \
+                (SCENE_FLAGS if os.path.basename(src).startswith("variant_") else []) + ["-c", "-o", obj, src]
             if verbose:
                 print(" ".join(cmd))
             procs.append((src, subprocess.Popen(cmd, cwd=CSRC)))

@@ -68,8 +68,7 @@ def main():
     src = os.path.join(csrc, f"variant_{a.variant}.hip")
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.join(tmp, "k.s")
-        cmd = (["hipcc"] + native._base_flags(os.path.join(csrc, "generated")) + native.ILP_FLAGS +
-               ["-DDUCK_ASM_MARKS"] + [f"-D{d}" for d in a.defines] +
+        cmd = (["hipcc"] + native.compile_flags() + ["-DDUCK_ASM_MARKS"] + [f"-D{d}" for d in a.defines] +
                ["--cuda-device-only", "-S", "-o", out, src])
         subprocess.check_call(cmd, cwd=csrc)
         text = open(out).read()
