@@ -149,6 +149,29 @@ int duck_policy_sample(int N, int A, const float* logits, unsigned long long see
 #define DUCK_POLICY_MAX_LAYERS 4
 int duck_policy_act(int N, int nlayers, const int* sizes, const float* const* W, const float* const* b,
                     const float* mean, const float* istd, const float* obs, float* logits, float* action, void* stream);
+/* duck_policy_act for K policies of one architecture in ONE launch (the fleet's tournament, sim2sim.FleetInfer with a
+ * list of policies): rows seg[k] .. seg[k+1] - 1 are served by policy k. seg is a HOST array [K + 1], copied into the
+ * launch's arguments as sizes is: seg[0] == 0, non-decreasing, seg[K] == N; a segment may be empty. All K policies
+ * share nlayers and sizes (duck_policy_act's limits). W[l] is device memory [K][sizes[l+1]][sizes[l]], b[l]
+ * [K][sizes[l+1]], mean and istd [K][sizes[0]] or both NULL; logits may be NULL.
+ * For every row r of segment k, logits[r] and action[r] are bit for bit what duck_policy_act writes for that row when
+ * called with policy k's parameters alone, and no word outside rows [0, N) is written. An MFMA tile shares one weight
+ * operand across its 16 rows, so a tile never mixes policies: a workgroup takes up to 16 consecutive rows of one
+ * segment (rows of the tile past the segment's end feed zeros and are not stored, as rows past N are), and a segment
+ * of n rows costs ceil(n / 16) workgroups.
+ * DUCK_EINVAL, with a message and no launch: K < 1 or K > DUCK_POLICY_MAX_POLICIES, a seg that breaks the three rules
+ * above, and every refusal of duck_policy_act. N == 0 launches nothing.
+ * duck_policy_multi_order(order) chooses how the block index maps to (policy, tile) for the launches enqueued from
+ * then on (process-wide) and returns the order that held before; any other value only asks. 0: policy-major.
+ * 1 (the default: the faster one at K = 8 and K = 64): each policy's tiles dealt to blocks congruent modulo 8, which
+ * have been observed to share an XCD, so that one L2 holds K / 8 policies' weights instead of all K. HIP promises
+ * nothing about placement: the order is a matter of speed only and the results are the same bits in both
+ * (DESIGN.md §9 "Policies" has the measurement). duck_policy_act itself is the K = 1 case of the same kernel. */
+#define DUCK_POLICY_MAX_POLICIES 64
+int duck_policy_act_multi(int N, int K, const int* seg, int nlayers, const int* sizes, const float* const* W,
+                          const float* const* b, const float* mean, const float* istd, const float* obs, float* logits,
+                          float* action, void* stream);
+int duck_policy_multi_order(int order);
 
 /* Episode bookkeeping around an env-step (brax EvalWrapper / EpisodeWrapper), one launch per env-step.
  * F = nmetrics + 2 columns per env: 0 = reward, 1..nmetrics = metrics[k][e] (row k at metrics + k * metrics_stride:

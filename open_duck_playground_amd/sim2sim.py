@@ -23,6 +23,8 @@ disturbances the training env has and the reference's deployment loop lacks: ``-
 ``--delay_seed``; and the flight recorder, ``--record_falls``, ``--record_post``, ``--record_out``,
 ``--record_max``: the last periods of every robot that fell, written to an ``.npz`` (the reference keeps what
 its loop saw in ``saved_obs``; the file holds the same observations and the state around them).
+``--policies P1 P2 ...`` puts several exported policies (the checkpoints of one training run) into one fleet,
+``--num_robots`` / K robots each on the same models, commands, push cells and delays, and ranks them.
 """
 
 from __future__ import annotations
@@ -304,7 +306,23 @@ class FleetInfer:
     were from the logged ones: over randomised models and a delay grid, which model the logged robot moves like.
     ``onnx_model_path=None`` is allowed with ``follow``: no policy is loaded. The start state is the loop's own (a log
     that starts elsewhere is the caller's to load with ``load_state``), and joint-encoder latency is not modelled.
-    With no log set (``following()`` False) the loop enqueues exactly the launches above."""
+    With no log set (``following()`` False) the loop enqueues exactly the launches above.
+
+    Several policies (``onnx_model_path`` a list or tuple of K paths, at most DUCK_POLICY_MAX_POLICIES, all of one
+    architecture and all with or all without a normaliser): the robots are policy-major, segment k --
+    ``policy_robots[k]`` robots, by default ``num_robots / K`` each -- is served by file k, and duck_policy_act_multi
+    takes duck_policy_act's place (no launch more; a tile of 16 rows never mixes policies). ``num_policies``,
+    ``policy_seg`` [K + 1] and ``policy_of`` [N] tell who is served by what. Robot r of segment k computes what a
+    single-policy fleet of that segment with ``robot_offset`` + seg[k] computes, bit for bit. A ``str`` path is
+    today's loop with today's launches; a list of one path goes through the new entry with K = 1. A list cannot be
+    combined with ``follow``.
+    Pairing: ``randomize=seed`` with several policies needs equal segments of S robots, draws S models and gives
+    every segment the same S columns of the randomisation record; ``tile_over_policies(a)`` repeats an [S, ...]
+    per-robot table K times for ``set_commands``, the schedule ids, ``set_pushes`` and ``set_latency``. Robot j of
+    every segment then has the same model, commands, push cell and fixed delays, and ``paired_wins`` compares the
+    policies scenario by scenario. Pairing does NOT cover the random streams -- the sensor noise, a push drawn from a
+    range (lo != hi) and delay jitter: they are keyed by the robot's global id, so they are independent between
+    segments and identically distributed, not common random numbers."""
 
     # control periods per captured graph (200 launches; 50 more with disturbances, 50 more with an IMU delay, 50 more
     # with a recorder: 400 at the most)
@@ -314,7 +332,8 @@ class FleetInfer:
                  reference_data: Optional[str] = None, standing: bool = False, device="cuda:0",
                  randomize: Optional[int] = None, command_schedule: Optional[tuple] = None,
                  pushes: Optional[tuple] = None, noise: Optional[tuple] = None, recorder: Optional[tuple] = None,
-                 robot_offset: int = 0, latency: Optional[tuple] = None, follow: Optional[tuple] = None):
+                 robot_offset: int = 0, latency: Optional[tuple] = None, follow: Optional[tuple] = None,
+                 policy_robots: Optional[Sequence[int]] = None):
         import ctypes as C
 
         from .native import DuckError, check
@@ -323,8 +342,19 @@ class FleetInfer:
         n = self.num_robots = int(num_robots)
         if n < 1:
             raise DuckError("num_robots must be >= 1")
-        pol = None
-        if onnx_model_path is None:
+        pol = pols = None
+        self.num_policies, self.policy_seg = 1, np.array([0, n], dtype=np.int32)
+        if isinstance(onnx_model_path, (list, tuple)):
+            onnx_model_path = [str(p) for p in onnx_model_path]
+            pols, self.policy_seg = load_policies(onnx_model_path, n, policy_robots, following=follow is not None)
+            self.num_policies = len(pols)
+            pol, sizes = pols[0], pols[0]["sizes"]
+            if randomize is not None and len(set(np.diff(self.policy_seg).tolist())) > 1:
+                raise DuckError(f"randomize pairs the policies on the same models: it needs equal segments, got "
+                                f"{np.diff(self.policy_seg).tolist()} robots")
+        elif policy_robots is not None:
+            raise DuckError("policy_robots splits the robots over a list of policies: onnx_model_path is not a list")
+        elif onnx_model_path is None:
             if follow is None:
                 raise DuckError("a fleet needs a policy (onnx_model_path) or a log to follow (follow=(log, ids))")
         else:
@@ -352,10 +382,18 @@ class FleetInfer:
 
         # the policy's dense layers on the device, pointers in host arrays (duck_policy_act's arguments)
         self._policy_args = None        # no policy loaded: the fleet can only follow a log
+        self._multi_args = None         # a list of policies: duck_policy_act_multi's (K, seg) in front of them
+        self.policy_of = np.repeat(np.arange(self.num_policies), np.diff(self.policy_seg)).astype(np.int32)
         if pol is not None:
             if sizes[0] != self.obs_size or pol["action_size"] != nu:
                 raise DuckError(f"policy maps {sizes[0]} -> {pol['action_size']}, the model's loop needs {self.obs_size} -> {nu}")
             up = lambda a: None if a is None else torch.tensor(a, dtype=torch.float32, device=dev).contiguous()  # noqa: E731
+            if pols is not None:   # the K policies' parameters stacked [K][...]
+                stack = lambda key, l=None: np.stack([p[key] if l is None else p[key][l] for p in pols])  # noqa: E731
+                pol = {"W": [stack("W", l) for l in range(len(sizes) - 1)], "b": [stack("b", l) for l in range(len(sizes) - 1)],
+                       "mean": None if pol["mean"] is None else stack("mean"),
+                       "istd": None if pol["istd"] is None else stack("istd")}
+                self._multi_args = (self.num_policies, (C.c_int * (self.num_policies + 1))(*self.policy_seg.tolist()))
             self._W, self._b = [up(w) for w in pol["W"]], [up(b) for b in pol["b"]]
             self._mean, self._istd = up(pol["mean"]), up(pol["istd"])
             self._policy_args = (len(sizes) - 1, (C.c_int * len(sizes))(*sizes),
@@ -373,9 +411,14 @@ class FleetInfer:
         self.acc, self.alive = z(n, HEADERS.consts["DUCK_FLEET_ACC_SIZE"]), torch.ones(n, dtype=torch.float32, device=dev)
         self.dr = None
         if randomize is not None:
-            self.dr = z(dr_layout(m.nbody, nu)["nfloat"] * n)
-            check(self._lib.duck_randomize(self._sim, n, self.dr.data_ptr(), int(randomize) & 0xFFFFFFFFFFFFFFFF, 0,
+            rows, K = dr_layout(m.nbody, nu)["nfloat"], self.num_policies
+            self.dr = z(rows * n)
+            s = n // K     # several policies: S models, every segment the same S columns of the record
+            draw = self.dr if K == 1 else z(rows * s)
+            check(self._lib.duck_randomize(self._sim, s, draw.data_ptr(), int(randomize) & 0xFFFFFFFFFFFFFFFF, 0,
                                            self._stream()), self._lib)
+            if K > 1:
+                self.dr.view(rows, K, s).copy_(draw.view(rows, 1, s).expand(rows, K, s))
         self.default_actuator = np.asarray(m.key_ctrl[m.names["key"].index("home")], dtype=np.float32)
         self.calls, self.graph = 0, None
         # the disturbances (include/duck_fleet.h duck_fleet_disturb): all off
@@ -471,11 +514,15 @@ class FleetInfer:
         self._launch("duck_fleet_observe", self.qpos, self.qvel, self.aux, self.ctl, self.obs, self.acc, self.alive)
 
     def policy(self):
-        """duck_policy_act on ``obs``."""
+        """duck_policy_act on ``obs``; of a fleet made from a list of policies, duck_policy_act_multi."""
         from .native import DuckError, lib
         if self._policy_args is None:
             raise DuckError("no policy is loaded (onnx_model_path=None): the fleet can only follow a log (set_log)")
         P = lib()   # the policy kernel ships with libduck.so only, the rest with the model's library
+        if self._multi_args is not None:
+            self._check(P.duck_policy_act_multi(self.num_robots, *self._multi_args, *self._policy_args, self.obs.data_ptr(),
+                                                None, self.action.data_ptr(), self._stream()), P)
+            return
         self._check(P.duck_policy_act(self.num_robots, *self._policy_args, self.obs.data_ptr(), None,
                                       self.action.data_ptr(), self._stream()), P)
 
@@ -587,6 +634,18 @@ class FleetInfer:
         """A view [N, width] of one field of the control record (``ctl_fields``)."""
         o, w = self.fields[name]
         return self.ctl[:, o:o + w]
+
+    def tile_over_policies(self, a) -> np.ndarray:
+        """An [S, ...] per-robot table of one segment repeated for every policy, [K S, ...] (``tile_over_policies``,
+        the module's function): robot j of every segment gets row j. Needs equal segments of S robots."""
+        from .native import DuckError
+        sizes = np.diff(self.policy_seg)
+        if len(set(sizes.tolist())) > 1:
+            raise DuckError(f"a table is tiled over equal segments, got {sizes.tolist()} robots")
+        a = np.asarray(a)
+        if a.ndim < 1 or a.shape[0] != int(sizes[0]):
+            raise DuckError(f"a per-robot table of a segment is [{int(sizes[0])}, ...], got {tuple(a.shape)}")
+        return tile_over_policies(a, self.num_policies)
 
     def set_commands(self, cmd) -> None:
         """``cmd`` [7] for every robot, or [N][7]."""
@@ -894,8 +953,11 @@ class FleetInfer:
         follow = None
         if self.following():   # the robot's own log (before the frame: set_log writes a command)
             follow = (self.log[int(self.log_id[robot])].cpu().numpy(), None)
+        made = dict(self._made_from)
+        if self._multi_args is not None:   # the robot's own policy file, through duck_policy_act: the same bits
+            made["onnx_model_path"] = made["onnx_model_path"][int(self.policy_of[robot])]
         r = FleetInfer(num_robots=1, randomize=None if self.dr is None else 0,
-                       robot_offset=self.robot_offset + robot, follow=follow, **self._made_from)
+                       robot_offset=self.robot_offset + robot, follow=follow, **made)
         if self.dr is not None:
             r.dr.copy_(self.dr.view(-1, self.num_robots)[:, robot])
         # the disturbances first, the frame last: set_command_schedule writes a command
@@ -990,16 +1052,18 @@ def command_grid(spec: str) -> np.ndarray:
     return out
 
 
-def grid_report(rep: Dict[str, np.ndarray], acc: np.ndarray, cells: np.ndarray, n_periods: int) -> list:
-    """Per command cell (robot r belongs to cell r mod the number of cells): the count, the share that
-    never fell, the mean tracked velocity and the rms errors over the cell's surviving periods."""
+def grid_report(rep: Dict[str, np.ndarray], acc: np.ndarray, cells: np.ndarray, n_periods: int, cell=None) -> list:
+    """Per command cell (robot r belongs to cell r mod the number of cells, or to ``cell[r]`` when the [N] ids are
+    given: a fleet of several policies tiles one segment's cells): the count, the share that never fell, the mean
+    tracked velocity and the rms errors over the cell's surviving periods."""
     out = []
+    cell = np.arange(len(acc)) % len(cells) if cell is None else np.asarray(cell)
     for c in range(len(cells)):
-        a = acc[c::len(cells)].astype(np.float64)
+        a = acc[cell == c].astype(np.float64)
         tot = a.sum(0)
         stat = (lambda v: float(v / tot[0])) if tot[0] > 0 else (lambda v: None)
         out.append({"command": [float(v) for v in cells[c][:3]], "count": int(len(a)),
-                    "survival_rate": float(np.mean(~rep["fell"][c::len(cells)])) if len(a) else None,
+                    "survival_rate": float(np.mean(~np.asarray(rep["fell"])[cell == c])) if len(a) else None,
                     "mean_periods": float(a[:, 0].mean()) if len(a) else None, "periods": int(n_periods),
                     "mean_vx": stat(tot[1]), "mean_vy": stat(tot[2]), "mean_wz": stat(tot[3]),
                     "rms_lin_err": None if stat(tot[4]) is None else float(np.sqrt(stat(tot[4]))),
@@ -1492,6 +1556,143 @@ def follow_round(fleet: "FleetInfer", rep: Dict[str, np.ndarray], survived, elit
     return {"best_total": best[0]["total"], "best": best}
 
 
+# --- several policies in one fleet (include/duck_ppo.h duck_policy_act_multi) ----------------------------
+def policy_segments(num_policies: int, num_robots: int, policy_robots=None) -> np.ndarray:
+    """``policy_seg`` [K + 1] int32: segment k is robots seg[k] .. seg[k + 1] - 1. ``policy_robots`` [K] gives the
+    lengths (0 is allowed), by default ``num_robots / K`` each. DuckError when the lengths are not K non-negative
+    integers that sum to ``num_robots``, or the default does not divide."""
+    from .native import DuckError
+    K, n = int(num_policies), int(num_robots)
+    if policy_robots is None:
+        if n % K:
+            raise DuckError(f"{n} robots do not split equally over {K} policies: give policy_robots")
+        lengths = np.full(K, n // K, dtype=np.int64)
+    else:
+        lengths = np.asarray(policy_robots)
+        if lengths.shape != (K,) or not np.issubdtype(lengths.dtype, np.integer) or (lengths < 0).any():
+            raise DuckError(f"policy_robots must be {K} non-negative integers, got {policy_robots!r}")
+        if int(lengths.sum()) != n:
+            raise DuckError(f"policy_robots {lengths.tolist()} sum to {int(lengths.sum())}, the fleet has {n} robots")
+    return np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
+
+
+def load_policies(paths, num_robots: int, policy_robots=None, following: bool = False):
+    """The K policy files of a fleet, validated on the host before any device work: (``dense_policy`` of every
+    file, ``policy_seg``). DuckError, naming the offending file, for an empty list, more than
+    DUCK_POLICY_MAX_POLICIES files, a list together with a followed log, a file outside duck_policy_act's limits,
+    layer sizes that differ from the first file's, and a normaliser in some files and not in others."""
+    from .native import DuckError
+    from .onnx_infer import OnnxGraph, dense_policy
+    from .ppo import POLICY_ACT_MAX_LAYERS, POLICY_ACT_MAX_WIDTH
+    paths, most = list(paths), HEADERS.consts["DUCK_POLICY_MAX_POLICIES"]
+    if not paths:
+        raise DuckError("a list of policies needs at least one file")
+    if len(paths) > most:
+        raise DuckError(f"a fleet holds at most {most} policies (DUCK_POLICY_MAX_POLICIES), got {len(paths)}: "
+                        f"{paths[most]!r} is one too many")
+    if following:
+        raise DuckError(f"a followed log takes the policy's place: it cannot be combined with a list of policies "
+                        f"({paths[0]!r}, ...)")
+    seg = policy_segments(len(paths), num_robots, policy_robots)
+    pols = []
+    for path in paths:
+        with open(path, "rb") as f:
+            pol = dense_policy(OnnxGraph(f.read()))
+        sizes = pol["sizes"]
+        if len(pol["W"]) > POLICY_ACT_MAX_LAYERS or max(sizes) > POLICY_ACT_MAX_WIDTH:
+            raise DuckError(f"{path!r}: policy layers {sizes} are outside duck_policy_act's limits (at most "
+                            f"{POLICY_ACT_MAX_LAYERS} layers, at most {POLICY_ACT_MAX_WIDTH} wide); there is no host fallback")
+        if pols and list(sizes) != list(pols[0]["sizes"]):
+            raise DuckError(f"{path!r} has layers {list(sizes)}, {paths[0]!r} has {list(pols[0]['sizes'])}: "
+                            "the policies of one fleet share one architecture")
+        if pols and (pol["mean"] is None) != (pols[0]["mean"] is None):
+            with_, without = (paths[0], path) if pol["mean"] is None else (path, paths[0])
+            raise DuckError(f"{with_!r} has an observation normaliser and {without!r} has none: all or none")
+        pols.append(pol)
+    return pols, seg
+
+
+def tile_over_policies(a, num_policies: int) -> np.ndarray:
+    """An [S, ...] per-robot table repeated ``num_policies`` times along its first axis, [K S, ...]: robot j of
+    every (equal) segment of a policy-major fleet gets row j."""
+    a = np.asarray(a)
+    return np.tile(a, (int(num_policies),) + (1,) * (a.ndim - 1))
+
+
+def policy_report(rep: Dict[str, np.ndarray], acc: np.ndarray, seg, n_periods: int, cells=None, push=None,
+                  delay=None) -> list:
+    """Per policy k (robots seg[k] .. seg[k + 1] - 1 of ``FleetInfer.report()``'s ``rep`` and of ``acc`` [N][6]):
+    the robot count, ``survival_rate``, ``mean_periods``, the rms tracking errors pooled over the segment's surviving
+    periods (None for an empty segment or one that survived no period), and the per-cell rows over the segment's
+    slice: ``"cells"`` = ``grid_report`` with ``cells`` [C][7]; ``"pushes"`` = ``push_report`` with ``push`` =
+    (push_cell [N], first, interval, window); ``"latency"`` = ``latency_report`` with ``delay`` = (delay_cell [N],
+    cells [D][2], jitter). The cell of a robot is what the fleet-wide tables say, sliced: with tiled tables a
+    segment's slice is the one-segment table."""
+    seg = np.asarray(seg, dtype=np.int64)
+    acc = np.asarray(acc)
+    fell = np.asarray(rep["fell"], dtype=bool)
+    out = []
+    for k in range(len(seg) - 1):
+        s = slice(int(seg[k]), int(seg[k + 1]))
+        a = acc[s].astype(np.float64)
+        cnt = len(a)
+        tot = a.sum(0) if cnt else np.zeros(acc.shape[1])
+        rms = (lambda v: float(np.sqrt(v / tot[0]))) if tot[0] > 0 else (lambda v: None)
+        sub = {key: np.asarray(v)[s] for key, v in rep.items()}
+        row = {"policy": k, "count": int(cnt), "survival_rate": float(np.mean(~fell[s])) if cnt else None,
+               "mean_periods": float(a[:, 0].mean()) if cnt else None, "periods": int(n_periods),
+               "rms_lin_err": rms(tot[4]), "rms_yaw_err": rms(tot[5])}
+        if cells is not None:
+            row["cells"] = grid_report(sub, acc[s], cells, n_periods)
+        if push is not None:
+            cell, first, interval, window = push
+            part = lambda v: np.asarray(v)[s] if np.ndim(v) else v  # noqa: E731
+            row["pushes"] = push_report(sub, np.asarray(cell)[s], part(first), part(interval), n_periods, window)
+        if delay is not None:
+            cell, dcells, jitter = delay
+            row["latency"] = latency_report(sub, acc[s], np.asarray(cell)[s], dcells, n_periods, jitter)
+        out.append(row)
+    return out
+
+
+def paired_wins(periods, num_policies: int) -> np.ndarray:
+    """[K][K] int64 from ``periods`` [K S] (policy-major, equal segments: the periods each robot survived): entry
+    [a][b] counts the scenarios j in which policy a's robot j survived strictly more periods than policy b's. Ties
+    count for neither, so [a][b] + [b][a] <= S and the diagonal is 0."""
+    from .native import DuckError
+    K = int(num_policies)
+    p = np.asarray(periods, dtype=np.float64)
+    if K < 1 or p.ndim != 1 or p.shape[0] % K:
+        raise DuckError(f"paired wins need periods [K S] of K = {K} equal segments, got {tuple(p.shape)}")
+    p = p.reshape(K, -1)
+    return (p[:, None, :] > p[None, :, :]).sum(-1).astype(np.int64)
+
+
+def rank_policies(rows) -> list:
+    """The policies of ``policy_report``'s rows, best first: ``survival_rate`` descending, then ``mean_periods``
+    descending, then ``rms_lin_err`` ascending with None / NaN last, then the index. A policy without robots
+    (rates None) ranks after every policy with some."""
+    def key(k):
+        r = rows[k]
+        num = lambda v: float("nan") if v is None else float(v)  # noqa: E731
+        s, p, e = num(r["survival_rate"]), num(r["mean_periods"]), num(r["rms_lin_err"])
+        return (np.isnan(s), -s if not np.isnan(s) else 0.0, np.isnan(p), -p if not np.isnan(p) else 0.0,
+                np.isnan(e), e if not np.isnan(e) else 0.0, k)
+    return sorted(range(len(rows)), key=key)
+
+
+def policies_doc(paths, rep: Dict[str, np.ndarray], acc: np.ndarray, seg, n_periods: int, cells=None, push=None,
+                 delay=None) -> dict:
+    """The three keys ``--policies`` adds to the command line's report: ``"policies"``, ``policy_report``'s rows
+    with each policy's ``"path"``; ``"ranking"``, the policy indices best first (``rank_policies``);
+    ``"paired_wins"``, the [K][K] matrix of ``paired_wins`` as lists."""
+    rows = policy_report(rep, acc, seg, n_periods, cells, push, delay)
+    for row, path in zip(rows, paths):
+        row["path"] = str(path)
+    return {"policies": rows, "ranking": rank_policies(rows),
+            "paired_wins": paired_wins(rep["periods"], len(rows)).tolist()}
+
+
 def build_parser():
     import argparse
     p = argparse.ArgumentParser(description="Run an exported policy in the deployment loop for a fleet of robots")
@@ -1510,6 +1711,9 @@ def build_parser():
     add_latency_arguments(p)
     add_recorder_arguments(p)
     add_follow_arguments(p)
+    p.add_argument("--policies", type=str, nargs="+", default=None, metavar="P",
+                   help="several exported policies in one fleet, --num_robots / K robots each on the same models, "
+                        "commands, pushes and delays; the report ranks them")
     return p
 
 
@@ -1517,8 +1721,15 @@ def parse_arguments(argv=None):
     """The command line's arguments; a flag that needs another one is a usage error."""
     p = build_parser()
     args = p.parse_args(argv)
-    if args.onnx_model_path is None and args.follow is None:
-        p.error("-o/--onnx_model_path is required (unless --follow LOG is given)")
+    if args.policies is not None:
+        if args.onnx_model_path is not None or args.follow is not None:
+            p.error("--policies P1 P2 ... takes the place of -o and cannot be combined with --follow")
+        if len(args.policies) > HEADERS.consts["DUCK_POLICY_MAX_POLICIES"]:
+            p.error(f"--policies takes at most {HEADERS.consts['DUCK_POLICY_MAX_POLICIES']} files")
+        if args.num_robots % len(args.policies):
+            p.error(f"--num_robots {args.num_robots} (the total) is not divisible by the {len(args.policies)} --policies")
+    elif args.onnx_model_path is None and args.follow is None:
+        p.error("-o/--onnx_model_path is required (unless --follow LOG or --policies P1 P2 ... is given)")
     try:
         follow_plan(args)
     except ValueError as e:
@@ -1532,28 +1743,40 @@ def parse_arguments(argv=None):
 
 def main(argv=None) -> int:
     import json
+    import copy
     args = parse_arguments(argv)
     cells = command_grid(args.command_grid)
-    plan = disturbance_plan(args, cells)
+    # several policies: every grid is built for one segment of num_robots / K robots and tiled over the K segments
+    K = 1 if args.policies is None else len(args.policies)
+    one = copy.copy(args)
+    one.num_robots = args.num_robots // K
+    over = lambda v: tile_over_policies(v, K) if K > 1 and np.ndim(v) else v  # noqa: E731
+    plan = disturbance_plan(one, cells)
     n_push = 1 if plan is None or plan["push_cells"] is None else len(plan["push_cells"])
-    delays = latency_plan(args, len(cells), n_push)
+    delays = latency_plan(one, len(cells), n_push)
     following = follow_plan(args)
     log = None if following is None else load_log(following["log"])
     if log is not None:
         args.periods = min(args.periods, int(log.shape[-2]))      # a run cannot pass the log's end
-    fleet = FleetInfer(args.model_path, args.onnx_model_path, args.num_robots, reference_data=args.reference_data,
+    fleet = FleetInfer(args.model_path, args.onnx_model_path if args.policies is None else list(args.policies),
+                       args.num_robots, reference_data=args.reference_data,
                        standing=args.standing, device=args.device, randomize=args.randomize,
                        follow=None if log is None else (log, None))
     if log is None:            # (a followed log brings its own commands)
-        fleet.set_commands(cells[np.arange(args.num_robots) % len(cells)])
+        fleet.set_commands(over(cells[np.arange(one.num_robots) % len(cells)]))
     if plan is not None:
         if plan["schedule"] is not None:
-            fleet.set_command_schedule(*plan["schedule"])
+            table, ids, seg_periods = plan["schedule"]
+            fleet.set_command_schedule(table, over(ids), seg_periods)
         if plan["pushes"] is not None:
+            plan["pushes"] = tuple(over(v) for v in plan["pushes"])
+            plan["push_cell"] = over(plan["push_cell"])
             fleet.set_pushes(*plan["pushes"])
         if args.noise:
             fleet.set_noise(args.noise, args.noise_seed)
     if delays is not None:
+        delays["cell"] = over(delays["cell"])
+        delays["latency"] = tuple(tuple(over(w) for w in v) if isinstance(v, tuple) else over(v) for v in delays["latency"])
         fleet.set_latency(*delays["latency"])
     if args.record_falls is not None:
         fleet.set_recorder(args.record_falls, args.record_post)
@@ -1585,7 +1808,8 @@ def main(argv=None) -> int:
             srep = fleet.score_report(weights)
             follow_doc["rounds"].append({"round": rnd, **follow_round(fleet, srep, fleet.report()["periods"], elite, delays)})
     rep = fleet.report()
-    rows = grid_report(rep, fleet.acc.cpu().numpy(), cells, args.periods)
+    rows = grid_report(rep, fleet.acc.cpu().numpy(), cells, args.periods,
+                       None if K == 1 else over(np.arange(one.num_robots) % len(cells)))
     doc = {"model_path": args.model_path, "onnx_model_path": args.onnx_model_path, "num_robots": args.num_robots,
            "periods": args.periods, "randomize": args.randomize, "standing": args.standing,
            "robot_periods_per_s": args.num_robots * args.periods / max(dt, 1e-9), "cells": rows}
@@ -1608,6 +1832,11 @@ def main(argv=None) -> int:
             written = int(len(arrays["robots"]))
         doc["recorder"] = {"depth": args.record_falls, "post": args.record_post, "fallen": int(rep["fell"].sum()),
                            "written": written}
+    if args.policies is not None:
+        doc.update(policies_doc(args.policies, rep, fleet.acc.cpu().numpy(), fleet.policy_seg, args.periods, cells,
+                                None if plan is None or plan["pushes"] is None else
+                                (plan["push_cell"], args.push_at, args.push_every, args.recovery_window),
+                                None if delays is None else (delays["cell"], delays["cells"], args.delay_jitter)))
     if follow_doc is not None:
         doc["follow"] = follow_doc
         if following["fit_out"]:
