@@ -100,6 +100,10 @@ int duck_set_step_mode(duck_sim* sim, int mode);
 int duck_step_kernel_for(const duck_sim* sim, int n_envs);
 /* debug: latency-mode event waits that gave up (a broken cross-wave schedule; must stay 0) */
 int duck_debug_lat_timeouts(const duck_sim* sim, unsigned* out, int reset);
+/* debug: the line search's row-activity flag (csrc/duck_lspairs.h) of x[0, n) in its two forms, device
+ * pointers: sel[i] = x[i] < 0 ? 1 : 0 by compare and select, sat[i] the saturating multiply the kernels use
+ * (tests/test_gpu_ls_pairs.py asserts equal words) */
+int duck_debug_ls_flag(int n, const float* x, float* sel, float* sat, void* stream);
 
 /* Sticky device error word of the handle (bits DUCK_DEVERR_*), set by a kernel that could not
  * complete its step correctly. It lives in host-mapped memory: duck_reset / duck_step /

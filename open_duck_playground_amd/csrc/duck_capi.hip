@@ -3,6 +3,7 @@
 // variant (variant_*.hip). Every entry returns DUCK_OK or a negative code with a
 // thread-local message; no entry allocates, synchronises or throws on the step path.
 #include "duck_common.h"
+#include "duck_lspairs.h"
 #include "duck_math.h"
 #include "../../include/duck_fleet.h"
 #include "../../include/duck_ppo.h"
@@ -60,6 +61,15 @@ struct Fnv {
 // per env over its F = nmetrics + 2 accumulator columns: plain fp32 adds in step order. It reads the step
 // kernel's outputs (reward, done, the metrics rows of the SoA state), so it lives in this unit and ships
 // with every model's library.
+// duck_debug_ls_flag: both forms of the line search's activity flag, each from the word in memory
+__global__ __launch_bounds__(256) void ls_flag_kernel(int n, const float* __restrict__ x, float* __restrict__ sel,
+                                                      float* __restrict__ sat) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  sel[i] = ls_flag_select(x[i]);
+  sat[i] = ls_flag_sat(x[i]);
+}
+
 __global__ __launch_bounds__(256) void episode_accumulate_kernel(int n, int nmetrics, const float* __restrict__ reward,
                                                                  const float* __restrict__ done,
                                                                  const float* __restrict__ metrics, int stride,
@@ -837,6 +847,15 @@ int duck_debug_lat_timeouts(const duck_sim* s, unsigned* out, int reset) {
   if (!s || !out) return duck_fail(DUCK_EINVAL, "bad argument");
   HIPCHECK(hipSetDevice(s->device));
   return kVariants[s->variant]->lat_timeouts(out, reset);
+}
+
+int duck_debug_ls_flag(int n, const float* x, float* sel, float* sat, void* stream) {
+  if (n < 0) return duck_fail(DUCK_EINVAL, "duck_debug_ls_flag: bad size");
+  if (n == 0) return DUCK_OK;
+  if (!x || !sel || !sat) return duck_fail(DUCK_EINVAL, "duck_debug_ls_flag: null pointer");
+  hipLaunchKernelGGL(ls_flag_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, x, sel, sat);
+  HIPCHECK(hipGetLastError());
+  return DUCK_OK;
 }
 
 // debug: the cycle counters of a stage-profile build into out[DUCK_STAGE_CYCLES_WORDS] (DUCK_EUNSUPPORTED otherwise)

@@ -16,6 +16,7 @@
 #include <utility>
 
 #include "duck_ldlpairs.h"
+#include "duck_lspairs.h"
 #include "duck_mcols.h"
 #include "duck_physics.h"
 
@@ -23,7 +24,6 @@ constexpr int TEAM = 16;
 constexpr int TEAM_WG = 16;  // envs (teams) per workgroup: 256 threads = 4 waves
 constexpr int TPB = TEAM * TEAM_WG;  // the block size of every env kernel
 typedef __attribute__((address_space(3))) int lds_int;
-typedef float f2v __attribute__((ext_vector_type(2)));
 typedef float f4v __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) f4v lds_f4;
 
@@ -3192,10 +3192,58 @@ struct TPhys {
     }
 #pragma unroll
     for (int k = 0; k < NLR + 4; k++) {
-      const float on = (R.ja[k] + alpha * R.v[k] < 0.0f) ? 1.0f : 0.0f;
+      const float on = ls_flag<LS_SAT>(R.ja[k] + alpha * R.v[k]);
       q0 = fmaf(on, R.Q0[k], q0);
       q1 = fmaf(on, R.Q1[k], q1);
       q2 = fmaf(on, R.Q2[k], q2);
+    }
+  }
+
+  // quad2 at two alphas at once (the line search's bracket ends al, ah): per one-sided row one packed FMA
+  // for x at both points, the 0/1 flag of each half (ls_flag), and three packed FMAs onto
+  // (q0, q1, q2) of both points; the friction row's x is one packed FMA, its zone selects stay per half.
+  // Each half is the operation quad2 does at that alpha -- the same FMA where quad2 has an FMA, the same
+  // select -- so every word is quad2's (profiles/r13_contraction_points.txt: where the scalar form
+  // contracts). The rows stay scalars: a row's word is splat over the pair by the operand modifier.
+  // The throughput kernel and physics_kernel (LAT = 0) take the pair; the latency kernels keep two quad2
+  // calls, the same words: step_kernel_lat_x2, held to 256 registers, spilled 7 registers with the pair where
+  // it spills 3 without (private segment 416 -> 432 B). -DDUCK_SCALAR_TWINS (a test build): two quad2 calls
+  // and the compare-and-select flag (duck_lspairs.h) everywhere.
+  // (ls_pairs<Md>(), duck_lspairs.h: the scenes that take the new flag and the pair at all)
+  static constexpr bool LS_SAT = ls_pairs<Md>(), LS_PAIRS = LAT == 0 && ls_pairs<Md>();
+  static DK void quad2_pair(Rows2& R, f2v alpha, f2v& q0, f2v& q1, f2v& q2) {
+    // The rows' words are made opaque here, inside the loop that calls this (no code): as loop invariants
+    // their splats are hoisted out of the loop as register pairs, one v_mov and one more live register per
+    // word; built next to the packed FMA a splat is the instruction's operand modifier on the scalar.
+    asm("" : "+v"(R.fja), "+v"(R.fv));
+#pragma unroll
+    for (int k = 0; k < NLR + 4; k++)
+      asm("" : "+v"(R.ja[k]), "+v"(R.v[k]), "+v"(R.Q0[k]), "+v"(R.Q1[k]), "+v"(R.Q2[k]));
+    {
+      const f2v ja = {R.fja, R.fja}, v = {R.fv, R.fv};
+      const f2v x = __builtin_elementwise_fma(alpha, v, ja);
+      float t0[2], t1[2], t2[2];
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+        const float xh = h ? x.y : x.x;
+        const bool lo = xh <= -R.frf, hi = xh >= R.frf, quad = !(lo || hi);
+        const float sg = lo ? -1.0f : 1.0f;
+        t0[h] = quad ? R.fQ0 : R.flin0 + sg * R.ffja;
+        t1[h] = quad ? R.fQ1 : sg * R.ffv;
+        t2[h] = quad ? R.fQ2 : 0.0f;
+      }
+      q0 += f2v{t0[0], t0[1]};
+      q1 += f2v{t1[0], t1[1]};
+      q2 += f2v{t2[0], t2[1]};
+    }
+#pragma unroll
+    for (int k = 0; k < NLR + 4; k++) {
+      const f2v ja = {R.ja[k], R.ja[k]}, v = {R.v[k], R.v[k]};
+      const f2v x = __builtin_elementwise_fma(alpha, v, ja);
+      const f2v on = {ls_flag<LS_SAT>(x.x), ls_flag<LS_SAT>(x.y)};
+      q0 = __builtin_elementwise_fma(on, f2v{R.Q0[k], R.Q0[k]}, q0);
+      q1 = __builtin_elementwise_fma(on, f2v{R.Q1[k], R.Q1[k]}, q1);
+      q2 = __builtin_elementwise_fma(on, f2v{R.Q2[k], R.Q2[k]}, q2);
     }
   }
 
@@ -3561,8 +3609,14 @@ struct TPhys {
       STAGE_COUNT_WAVE0(ST_N_LS_WAVE_ITERS, 1ull);
       const float al = lo.alpha - lo.d0 / lo.d1, ah = hi.alpha - hi.d0 / hi.d1, am = 0.5f * (lo.alpha + hi.alpha);
       float a0 = 0, a1 = 0, a2 = 0, b0 = 0, b1 = 0, b2 = 0, c0 = 0, c1 = 0, c2 = 0;
-      quad2(R, al, a0, a1, a2);
-      quad2(R, ah, b0, b1, b2);
+      if constexpr (LS_PAIRS) {
+        f2v p0 = {0.0f, 0.0f}, p1 = {0.0f, 0.0f}, p2 = {0.0f, 0.0f};
+        quad2_pair(R, f2v{al, ah}, p0, p1, p2);
+        a0 = p0.x; b0 = p0.y; a1 = p1.x; b1 = p1.y; a2 = p2.x; b2 = p2.y;
+      } else {
+        quad2(R, al, a0, a1, a2);
+        quad2(R, ah, b0, b1, b2);
+      }
       quad2(R, am, c0, c1, c2);
       const Pt lo_next = mk(al, a0, a1, a2), hi_next = mk(ah, b0, b1, b2), mid = mk(am, c0, c1, c2);
       const bool s1 = (lo.d0 > 0.0f) || (lo.d0 < lo_next.d0);
