@@ -116,10 +116,9 @@ int duck_device_error(duck_sim* sim, unsigned* out, int clear);
 
 /* Joystick.step (+ wrappers if cfg->auto_reset). `dr` (nullable) = per-env randomised
  * model values (duck_dr_layout, SoA [k][n_envs]) written by duck_randomize. `reward`,
- * `done` are [n_envs]. `scratch` (nullable unless feet can collide) = n_envs*nv*nv floats
- * for the rare dense-Hessian path. */
+ * `done` are [n_envs]. */
 int duck_step(duck_sim* sim, int n_envs, float* fstate, int32_t* istate, const float* dr, const float* action,
-              float* obs, float* priv, float* reward, float* done, float* scratch, void* stream);
+              float* obs, float* priv, float* reward, float* done, void* stream);
 
 /* domain_randomize: fill dr (SoA [duck_dr_layout.nfloat][n_envs]) for global env ids
  * [env_offset, env_offset + n_envs). */
@@ -129,7 +128,7 @@ int duck_randomize(duck_sim* sim, int n_envs, float* dr, uint64_t seed, int64_t 
  * ctrl [nu]. n_substeps = 0 runs one forward pass without integration. `aux` (nullable)
  * receives the last substep's forward record (duck_aux_size floats per env, SoA). */
 int duck_physics_step(duck_sim* sim, int n_envs, float* qpos, float* qvel, float* qacc_warmstart, const float* ctrl,
-                      const float* dr, int n_substeps, float* aux, float* scratch, void* stream);
+                      const float* dr, int n_substeps, float* aux, void* stream);
 
 #ifdef __cplusplus
 }

@@ -791,15 +791,14 @@ int duck_reset(duck_sim* s, int n, float* fstate, int32_t* istate, const uint8_t
 }
 
 int duck_step(duck_sim* s, int n, float* fstate, int32_t* istate, const float* dr, const float* action, float* obs,
-              float* priv, float* reward, float* done, float* scratch, void* stream) {
+              float* priv, float* reward, float* done, void* stream) {
   g_err.clear();
   if (!s || n < 0 || !fstate || !istate || !action || !obs || !priv || !reward || !done)
     return duck_fail(DUCK_EINVAL, "bad argument");
   if (*s->err_h) return device_error_fail(s);
   if (n == 0) return DUCK_OK;
   HIPCHECK(hipSetDevice(s->device));
-  return kVariants[s->variant]->step(s, n, fstate, istate, dr, action, obs, priv, reward, done, scratch,
-                                     (hipStream_t)stream);
+  return kVariants[s->variant]->step(s, n, fstate, istate, dr, action, obs, priv, reward, done, (hipStream_t)stream);
 }
 
 int duck_randomize(duck_sim* s, int n, float* dr, uint64_t seed, int64_t env_offset, void* stream) {
@@ -811,13 +810,13 @@ int duck_randomize(duck_sim* s, int n, float* dr, uint64_t seed, int64_t env_off
 }
 
 int duck_physics_step(duck_sim* s, int n, float* qpos, float* qvel, float* warm, const float* ctrl, const float* dr,
-                      int nsub, float* aux, float* scratch, void* stream) {
+                      int nsub, float* aux, void* stream) {
   g_err.clear();
   if (!s || n < 0 || !qpos || !qvel || !warm || !ctrl || nsub < 0) return duck_fail(DUCK_EINVAL, "bad argument");
   if (*s->err_h) return device_error_fail(s);
   if (n == 0) return DUCK_OK;
   HIPCHECK(hipSetDevice(s->device));
-  return kVariants[s->variant]->physics(s, n, qpos, qvel, warm, ctrl, dr, nsub, aux, scratch, (hipStream_t)stream);
+  return kVariants[s->variant]->physics(s, n, qpos, qvel, warm, ctrl, dr, nsub, aux, (hipStream_t)stream);
 }
 
 int duck_set_step_mode(duck_sim* s, int mode) {

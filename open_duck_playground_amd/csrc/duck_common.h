@@ -57,10 +57,10 @@ struct VariantOps {
   int (*reset)(duck_sim*, int n, float* fs, int32_t* is, const uint8_t* mask, uint64_t seed, int64_t env_offset,
                const float* dr, float* obs, float* priv, hipStream_t st);
   int (*step)(duck_sim*, int n, float* fs, int32_t* is, const float* dr, const float* action, float* obs,
-              float* priv, float* reward, float* done, float* scratch, hipStream_t st);
+              float* priv, float* reward, float* done, hipStream_t st);
   int (*randomize)(duck_sim*, int n, float* dr, uint64_t seed, int64_t env_offset, hipStream_t st);
   int (*physics)(duck_sim*, int n, float* qpos, float* qvel, float* warm, const float* ctrl, const float* dr,
-                 int nsub, float* aux, float* scratch, hipStream_t st);
+                 int nsub, float* aux, hipStream_t st);
   int (*stage_cycles)(unsigned long long* out, int reset);
   int (*lat_timeouts)(unsigned* out, int reset);
   size_t (*lds_bytes_lat)();

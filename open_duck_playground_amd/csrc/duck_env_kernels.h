@@ -33,7 +33,6 @@ struct KArgs {
   float* priv;
   float* reward;
   float* done;
-  float* scratch;
   const uint8_t* mask;
   uint64_t seed;
   int64_t env_offset;
@@ -67,9 +66,9 @@ DK lds_float* env_slice(float* lds, int t) {
 // scenes' step_kernel and phys_step_dni compile to different instructions (same count, other address
 // arithmetic in the contact stores)
 template <class Md>
-DK void phys_step(lds_float* L, int lane, bool integrate, bool want_out, float* aux, int aux_stride, float* scratch,
-                  int sstride, const float* hfield) {
-  TPhys<Md>::step(L, lane, integrate, want_out, aux, aux_stride, scratch, sstride, hfield);
+DK void phys_step(lds_float* L, int lane, bool integrate, bool want_out, float* aux, int aux_stride,
+                  const float* hfield) {
+  TPhys<Md>::step(L, lane, integrate, want_out, aux, aux_stride, hfield);
 }
 
 // the physics_kernel (mjx_env.step / mjx.forward parity entry) runs its substeps through one
@@ -79,8 +78,8 @@ DK void phys_step(lds_float* L, int lane, bool integrate, bool want_out, float* 
 // ahead of an exec restore)
 template <class Md>
 __device__ __noinline__ void phys_step_dni(lds_float* L, int lane, bool integrate, bool want_out, float* aux,
-                                           int aux_stride, float* scratch, int sstride, const float* hfield) {
-  phys_step<Md>(L, lane, integrate, want_out, aux, aux_stride, scratch, sstride, hfield);
+                                           int aux_stride, const float* hfield) {
+  phys_step<Md>(L, lane, integrate, want_out, aux, aux_stride, hfield);
 }
 
 struct Col {  // SoA accessor for env e
@@ -319,7 +318,7 @@ __global__ void __launch_bounds__(TPB) reset_kernel(KArgs A) {
   const float vr = Lo.task == DUCK_TASK_STANDING ? 0.5f : 0.05f;
   for (int k = 0; k < 6; k++) L[Ly::QVEL + k] = r.uniform(RSLOT_QVEL + k, -vr, vr);
   for (int a = 0; a < NU; a++) L[Ly::CTRL + a] = L[Ly::QPOS + c.actuator_qposadr[a]];
-  phys_step<Md>(L, lane, false, true, nullptr, 0, A.scratch ? A.scratch + e : nullptr, A.n, A.hfield);
+  phys_step<Md>(L, lane, false, true, nullptr, 0, A.hfield);
   float cmd[7];
   sample_command(c, r, RSLOT_CMD, cmd);
   const float push_interval = r.uniform(RSLOT_PUSH, c.push_interval_range[0], c.push_interval_range[1]);
@@ -455,13 +454,11 @@ DK void step_env(const KArgs& A, int e, int lane, lds_float* L, const FA& F, con
   load_dyn_team<Md, LAT>(A, e, L, lane);
   TSYNC();
   // physics (joystick.py:420)
-  float* scr = A.scratch ? A.scratch + e : nullptr;
   STAGE_MARK(ST_ENV_PRE);
   if constexpr (LAT) {
     // wave 0's share of each substep (the paired kernel: wave A's); the other waves run theirs in
     // step_kernel_lat. The env code below reads the last substep's state and sensors: wait for Euler
     using TPL = TPhys<Md, LAT>;
-    (void)scr;
     LAT_T(43, 5);
     for (int s = 0; s < c.n_substeps; s++) {
       if constexpr (LAT == 2) TPL::lat2_a(L, lane, s, A.hfield);
@@ -471,7 +468,7 @@ DK void step_env(const KArgs& A, int e, int lane, lds_float* L, const FA& F, con
     LAT_T(44, 5);
   } else {
     for (int s = 0; s < c.n_substeps; s++)
-      phys_step<Md>(L, lane, true, s == c.n_substeps - 1, nullptr, 0, scr, n, A.hfield);
+      phys_step<Md>(L, lane, true, s == c.n_substeps - 1, nullptr, 0, A.hfield);
   }
   STAGE_RESET();
   for (int a = lane; a < NU; a += TEAM) {
@@ -814,7 +811,6 @@ __device__ __forceinline__ void step_lat_body(KArgs A) {
   if (e < n) {
     lds_float* const L = env_slice<Md, LAT>(lds, t);
     const int ns = A.cfg.n_substeps;
-    float* scr = A.scratch ? A.scratch + e : nullptr;
     auto env_code = [&]() {
       const Col G{A.fs + e, n};
       lds_float* esp = (lds_float*)(lds + TL::ES + t * TL::ESTRIDE);
@@ -828,13 +824,13 @@ __device__ __forceinline__ void step_lat_body(KArgs A) {
       if ((wave & 1) == 0) {
         env_code();
       } else {
-        for (int s = 0; s < ns; s++) TPL::lat2_b(L, lane, s, true, s == ns - 1, scr, n);
+        for (int s = 0; s < ns; s++) TPL::lat2_b(L, lane, s, true, s == ns - 1);
       }
     } else {
       if (wave == 0) {
         env_code();
       } else if (wave == 1) {
-        for (int s = 0; s < ns; s++) TPL::lat_r1(L, lane, s, true, s == ns - 1, scr, n);
+        for (int s = 0; s < ns; s++) TPL::lat_r1(L, lane, s, true, s == ns - 1);
       } else if (wave == 2) {
         for (int s = 0; s < ns; s++) TPL::lat_r2(L, lane, s, A.hfield);
       } else {
@@ -916,10 +912,9 @@ __global__ void __launch_bounds__(TPB) physics_kernel(KArgs A, float* qpos_g, fl
   for (int a = 0; a < Md::NU; a++) L[Ly::CTRL + a] = ctrl_g[(size_t)a * n + e];
   load_dyn<Md>(A, e, L);
   float* ax = aux ? aux + e : nullptr;
-  float* scr = A.scratch ? A.scratch + e : nullptr;
   // nsub = 0: one forward (mjx.forward), no integration
   const int ns = nsub > 0 ? nsub : 1;
-  for (int s = 0; s < ns; s++) phys_step_dni<Md>(L, lane, nsub > 0, s == ns - 1, ax, n, scr, n, A.hfield);
+  for (int s = 0; s < ns; s++) phys_step_dni<Md>(L, lane, nsub > 0, s == ns - 1, ax, n, A.hfield);
   for (int i = 0; i < Md::NQ; i++) qpos_g[(size_t)i * n + e] = L[Ly::QPOS + i];
   for (int i = 0; i < Md::NV; i++) { qvel_g[(size_t)i * n + e] = L[Ly::QVEL + i]; warm_g[(size_t)i * n + e] = L[Ly::WARM + i]; }
 }
@@ -1014,10 +1009,10 @@ static int launch_reset(duck_sim* s, int n, float* fs, int32_t* is, const uint8_
 
 template <class Md>
 static int launch_step(duck_sim* s, int n, float* fs, int32_t* is, const float* dr, const float* action, float* obs,
-                       float* priv, float* reward, float* done, float* scratch, hipStream_t st) {
+                       float* priv, float* reward, float* done, hipStream_t st) {
   KArgs A = make_args(s, n);
   A.fs = fs; A.is = is; A.dr = dr; A.action = action; A.obs = obs; A.priv = priv;
-  A.reward = reward; A.done = done; A.scratch = scratch;
+  A.reward = reward; A.done = done;
   if (s->lay.first_qpos != TLay<Md>::HOT) return duck_fail(DUCK_EINVAL, "state layout does not match the kernel's hot-state size");
   // the kernel for this batch (step_kernel_choice: AUTO takes the latency kernel while the batch
   // leaves a CU per 4 envs, the paired one while it leaves a CU per 8 -- each latency workgroup takes a
@@ -1062,11 +1057,10 @@ static int launch_randomize(duck_sim* s, int n, float* dr, uint64_t seed, int64_
 
 template <class Md>
 static int launch_physics(duck_sim* s, int n, float* qpos, float* qvel, float* warm, const float* ctrl, const float* dr,
-                          int nsub, float* aux, float* scratch, hipStream_t st) {
+                          int nsub, float* aux, hipStream_t st) {
   const dim3 grid((n + TEAM_WG - 1) / TEAM_WG), block(TPB);
   KArgs A = make_args(s, n);
   A.dr = dr;
-  A.scratch = scratch;
   hipLaunchKernelGGL((physics_kernel<Md>), grid, block, lds_bytes<Md>(), st, A, qpos, qvel, warm, ctrl, nsub, aux);
   HIPCHECK(hipGetLastError());
   return DUCK_OK;

@@ -3250,16 +3250,156 @@ struct TPhys {
   // mjx solver.solve: warm-start choice, then Md::iterations Newton steps (the Open Duck scenes
   // use 1; a model compiled with more iterates to the MJX stopping rule on the cost improvement)
   // Mc: M as full symmetric columns in registers for every M.x of the solver
-  static DK void solve(LP L, int lane, float* scratch, int stride, const float (*Mc)[NV]) {
+  static DK void solve(LP L, int lane, const float (*Mc)[NV]) {
     STAGE_T0();
     const float g0 = warm_start(L, lane, Mc);
     STAGE_AGAIN(21, (void)warm_start(L, lane, Mc));
-    newton(L, lane, scratch, stride, Mc, g0);
+    newton(L, lane, Mc, g0);
   }
-  // latency mode: the warm start's products that need only qacc_warmstart (its feet motions, M and J
-  // products, constraint costs) run while wave 3 solves for qacc_smooth; then those of qacc_smooth
-  // and the choice. The same operations in the same order as warm_start's fused pass: same values.
-  // (a0 needs only qacc_warmstart and M: it runs before the rows are there; a1 the rows' costs)
+  // ---- warm start vs smooth acceleration (mjx solver.solve's start) ----
+  // The rows' costs of a start (warm_rows) and the choice between the two (warm_choose) are written once.
+  // The throughput kernel and physics_kernel run both starts' chains in one fused pass (warm_start). The
+  // latency kernels split the pass, so that what needs only qacc_warmstart runs while qacc_smooth is still
+  // being solved for: warm_start_a0 (the products of qacc_warmstart: they need M only, not the rows),
+  // warm_start_a1 (the rows' warm chain), warm_start_b (the smooth chain and the choice). Each value comes
+  // from the same expression in every form, so the kernels agree bit for bit
+  // (tests/test_gpu_env.py::test_latency_mode_matches_throughput_mode).
+  //
+  // The forms differ in one thing only: when the words may be read. The shared code therefore takes them
+  // through a view.
+  //   WarmPre   the fused pass: every word read ahead of the products and their sync, whose work covers the
+  //             round trip. One wave runs the whole substep there, and each word's writer has ended with a
+  //             sync of its own (the table in warm_start).
+  //   WarmLive  the latency kernels: each word read where it is used. The rows' words (RD, AREF, LSGN, the
+  //             JxIn words) are written by another wave and may be read only after ev_wait(EV_ROWS), QSM only
+  //             after ev_wait(EV_QSM) (the paired kernel: after the wave's own smooth_solve). The callers
+  //             wait and then call: no read of a view may move above the call that makes it. (Reading a
+  //             half's words at its top instead cost step_kernel_lat_x2 four more spilled registers.)
+  // One record for the three kinds of row, so that a view has one shape of accessor: a contact edge has only
+  // (D, ar) and a limit row no f; the fields a kind or a chain does not use are constants that fold away.
+  struct RowIn { float D, f, sg, ar, w, q; };  // a row's 1/R, friction loss, limit sign, aref; its dof's two starts
+  struct DofIn { float fsm, w, q; };           // a dof's qfrc_smooth and two starts (the Gauss term)
+  template <bool W, bool S>  // (the starts whose words are read: W qacc_warmstart, S qacc_smooth)
+  struct WarmLive {
+    LP L;
+    int lane, slot;  // (slot: the lane's contact slot, 0 on the lanes past the last: one value for every use)
+    DK WarmLive(LP L, int lane) : L(L), lane(lane), slot(lane < NCON ? lane : 0) {}
+    DK RowIn fric() const {
+      const int r = lane < NFRIC ? lane : 0, i = fric_dof(r);
+      return {L[Ly::RD + r], L[Ly::DFRIC + i], 1.0f, L[Ly::AREF + r], W ? L[Ly::WARM + i] : 0.0f,
+              S ? L[Ly::QSM + i] : 0.0f};
+    }
+    DK RowIn lim(int m) const {
+      const int rl = lane + TEAM * m, r = rl < NLIM ? rl : 0, i = lim_dof(r);
+      return {L[Ly::RD + R_LIM + r], 0.0f, L[Ly::LSGN + r], L[Ly::AREF + R_LIM + r], W ? L[Ly::WARM + i] : 0.0f,
+              S ? L[Ly::QSM + i] : 0.0f};
+    }
+    DK JxIn jx() const { return jx_load(L, slot >> 2, slot); }
+    DK RowIn con(int e) const {
+      // (the constants first: they fold into the access's offset)
+      return {L[Ly::RD + R_CON + 4 * slot + e], 0.0f, 1.0f, L[Ly::AREF + R_CON + 4 * slot + e], 0.0f, 0.0f};
+    }
+    DK DofIn dof(int s) const {
+      const int c = TEAM * s + lane, i = c < NV ? c : 0;
+      return {L[Ly::FSM + i], L[Ly::WARM + i], L[Ly::QSM + i]};
+    }
+  };
+  struct WarmPre {
+    RowIn f, l[NLR], c[4];
+    JxIn j;
+    DofIn d[NC];
+    DK WarmPre(const WarmLive<true, true>& in) {
+      f = in.fric();
+#pragma unroll
+      for (int m = 0; m < NLR; m++) l[m] = in.lim(m);
+      j = in.jx();
+      for (int e = 0; e < 4; e++) c[e] = in.con(e);
+#pragma unroll
+      for (int s = 0; s < NC; s++) d[s] = in.dof(s);
+    }
+    DK RowIn fric() const { return f; }
+    DK RowIn lim(int m) const { return l[m]; }
+    DK const JxIn& jx() const { return j; }
+    DK RowIn con(int e) const { return c[e]; }
+    DK DofIn dof(int s) const { return d[s]; }
+  };
+  // the cost of a one-sided row (limit, contact edge) at jx = J.x - aref
+  // (a body of its own lines: tools/fpc_bisect.py puts a function's pragma behind the line that opens it)
+  static DK float side_cost(float D, float jx) {
+    return jx < 0.0f ? 0.5f * D * jx * jx : 0.0f;
+  }
+  // the costs of the lane's rows (its friction row, limit rows and the 4 edges of its contact slot) at
+  // qacc_warmstart (W: partial sum cwp, J.x - aref into JA) and at qacc_smooth (S: csp, JV); SL / SR the
+  // feet's motions at qacc_warmstart, SL2 / SR2 at qacc_smooth
+  template <bool W, bool S, class V>
+  static DK void warm_rows(LP L, int lane, const V& in, const float* SL, const float* SR, const float* SL2,
+                           const float* SR2, float& cwp, float& csp) {
+    cwp = csp = 0.0f;
+    {
+      // branchless (no lane-divergent region: see TL::SINK)
+      const bool fr = lane < NFRIC;
+      const int r = fr ? lane : 0;
+      const RowIn x = in.fric();
+      const float jw = x.w - x.ar, js = x.q - x.ar;
+      if constexpr (W) cwp += fr ? fric_cost(x.D, jw, x.f) : 0.0f;
+      if constexpr (S) csp += fr ? fric_cost(x.D, js, x.f) : 0.0f;
+      if constexpr (W) L[fr ? Ly::JA + r : TL::SINK + lane] = jw;
+      if constexpr (S) L[fr ? Ly::JV + r : TL::SINK + TEAM + lane] = js;
+    }
+#pragma unroll
+    for (int m = 0; m < NLR; m++) {
+      const int r = lane + TEAM * m;
+      if (NLIM % TEAM != 0 && m == NLR - 1 && r >= NLIM) continue;
+      const RowIn x = in.lim(m);
+      const float jw = x.sg * x.w - x.ar, js = x.sg * x.q - x.ar;
+      if constexpr (W) cwp += side_cost(x.D, jw);
+      if constexpr (S) csp += side_cost(x.D, js);
+      if constexpr (W) L[Ly::JA + R_LIM + r] = jw;
+      if constexpr (S) L[Ly::JV + R_LIM + r] = js;
+    }
+    if (lane < NCON) {
+      const JxIn& jx = in.jx();
+      float vw[4] = {}, vs[4] = {};
+      if constexpr (W) contact_jx(jx, SL, SR, vw);
+      if constexpr (S) contact_jx(jx, SL2, SR2, vs);
+      for (int e = 0; e < 4; e++) {
+        const int row = R_CON + 4 * lane + e;
+        const RowIn x = in.con(e);
+        const float jw = vw[e] - x.ar, js = vs[e] - x.ar;
+        if constexpr (W) cwp += side_cost(x.D, jw);
+        if constexpr (S) csp += side_cost(x.D, js);
+        if constexpr (W) L[Ly::JA + row] = jw;
+        if constexpr (S) L[Ly::JV + row] = js;
+      }
+    }
+  }
+  // the end of the pass: the Gauss term of qacc_warmstart, 0.5 (M qw - f).(qw - qs), the costs summed over
+  // the team, and the cheaper start into QACC / MA / JA. Returns the Gauss cost at that start.
+  template <class V>
+  static DK float warm_choose(LP L, int lane, const V& in, float cwp, float csp, bool& warm) {
+    float gwp = 0.0f;
+#pragma unroll
+    for (int s = 0; s < NC; s++) {
+      const int i = TEAM * s + lane;
+      if (NV % TEAM != 0 && s == NC - 1 && i >= NV) continue;
+      const DofIn d = in.dof(s);
+      gwp += 0.5f * (L[Ly::MA + i] - d.fsm) * (d.w - d.q);
+    }
+    const float gw = tsum(gwp);
+    const float cw = gw + tsum(cwp), cs = tsum(csp);
+    float g0;
+    warm = cw < cs;
+    if (warm) {
+      team_for<NV>(lane, [&](int i) { L[Ly::QACC + i] = L[Ly::WARM + i]; });
+      g0 = gw;
+    } else {
+      team_for<NV>(lane, [&](int i) { L[Ly::QACC + i] = L[Ly::QSM + i]; L[Ly::MA + i] = L[Ly::FSM + i]; });
+      team_for<NROW>(lane, [&](int r) { L[Ly::JA + r] = L[Ly::JV + r]; });
+      g0 = 0.0f;  // gauss(qacc_smooth) = 0.5 (M qs - f).(qs - qs) = 0
+    }
+    TSYNC();
+    return g0;
+  }
   static DK void warm_start_a0(LP L, int lane, const float (*Mc)[NV], float* SL, float* SR) {
     float sw, ss;
     spatial2(L, lane, Ly::WARM, -1, sw, ss);
@@ -3271,119 +3411,31 @@ struct TPhys {
     sp_bcast(sw, SL, SR);
   }
   static DK void warm_start_a1(LP L, int lane, const float* SL, const float* SR, float& cwp) {
-    cwp = 0.0f;
-    {
-      const bool fr = lane < NFRIC;
-      const int r = fr ? lane : 0, i = fric_dof(r);
-      const float D = L[Ly::RD + r], f = L[Ly::DFRIC + i], ar = L[Ly::AREF + r];
-      const float jw = L[Ly::WARM + i] - ar;
-      cwp += fr ? fric_cost(D, jw, f) : 0.0f;
-      L[fr ? Ly::JA + r : TL::SINK + lane] = jw;
-    }
-    team_for<NLIM>(lane, [&](int r) {
-      const int i = lim_dof(r), row = R_LIM + r;
-      const float D = L[Ly::RD + row], sg = L[Ly::LSGN + r], ar = L[Ly::AREF + row];
-      const float jw = sg * L[Ly::WARM + i] - ar;
-      cwp += jw < 0.0f ? 0.5f * D * jw * jw : 0.0f;
-      L[Ly::JA + row] = jw;
-    });
-    if (lane < NCON) {
-      float vw[4];
-      contact_jx(L, lane >> 2, lane, SL, SR, vw);
-      for (int e = 0; e < 4; e++) {
-        const int row = R_CON + 4 * lane + e;
-        const float D = L[Ly::RD + row], ar = L[Ly::AREF + row];
-        const float jw = vw[e] - ar;
-        cwp += jw < 0.0f ? 0.5f * D * jw * jw : 0.0f;
-        L[Ly::JA + row] = jw;
-      }
-    }
+    float csp;
+    warm_rows<true, false>(L, lane, WarmLive<true, false>(L, lane), SL, SR, nullptr, nullptr, cwp, csp);
   }
   static DK float warm_start_b(LP L, int lane, float cwp, bool& warm) {
     float ss, s2;
     spatial2(L, lane, Ly::QSM, -1, ss, s2);
     TSYNC();
-    float SL2[6], SR2[6];
+    float SL2[6], SR2[6], cw0, csp;
     sp_bcast(ss, SL2, SR2);
-    float csp = 0.0f, gwp = 0.0f;
-    {
-      const bool fr = lane < NFRIC;
-      const int r = fr ? lane : 0, i = fric_dof(r);
-      const float D = L[Ly::RD + r], f = L[Ly::DFRIC + i], ar = L[Ly::AREF + r];
-      const float js = L[Ly::QSM + i] - ar;
-      csp += fr ? fric_cost(D, js, f) : 0.0f;
-      L[fr ? Ly::JV + r : TL::SINK + TEAM + lane] = js;
-    }
-    team_for<NLIM>(lane, [&](int r) {
-      const int i = lim_dof(r), row = R_LIM + r;
-      const float D = L[Ly::RD + row], sg = L[Ly::LSGN + r], ar = L[Ly::AREF + row];
-      const float js = sg * L[Ly::QSM + i] - ar;
-      csp += js < 0.0f ? 0.5f * D * js * js : 0.0f;
-      L[Ly::JV + row] = js;
-    });
-    if (lane < NCON) {
-      float vs[4];
-      contact_jx(L, lane >> 2, lane, SL2, SR2, vs);
-      for (int e = 0; e < 4; e++) {
-        const int row = R_CON + 4 * lane + e;
-        const float D = L[Ly::RD + row], ar = L[Ly::AREF + row];
-        const float js = vs[e] - ar;
-        csp += js < 0.0f ? 0.5f * D * js * js : 0.0f;
-        L[Ly::JV + row] = js;
-      }
-    }
-    team_for<NV>(lane, [&](int i) { gwp += 0.5f * (L[Ly::MA + i] - L[Ly::FSM + i]) * (L[Ly::WARM + i] - L[Ly::QSM + i]); });
-    const float gw = tsum(gwp);
-    const float cw = gw + tsum(cwp), cs = tsum(csp);
-    float g0;
-    warm = cw < cs;
-    if (warm) {
-      team_for<NV>(lane, [&](int i) { L[Ly::QACC + i] = L[Ly::WARM + i]; });
-      g0 = gw;
-    } else {
-      team_for<NV>(lane, [&](int i) { L[Ly::QACC + i] = L[Ly::QSM + i]; L[Ly::MA + i] = L[Ly::FSM + i]; });
-      team_for<NROW>(lane, [&](int r) { L[Ly::JA + r] = L[Ly::JV + r]; });
-      g0 = 0.0f;
-    }
-    TSYNC();
-    return g0;
+    const WarmLive<false, true> in(L, lane);
+    warm_rows<false, true>(L, lane, in, nullptr, nullptr, SL2, SR2, cw0, csp);
+    return warm_choose(L, lane, in, cwp, csp, warm);
   }
-  // warm start vs smooth acceleration (mjx solver.solve's start): returns the Gauss cost at the start
+  // the fused pass: returns the Gauss cost at the start
   static DK float warm_start(LP L, int lane, const float (*Mc)[NV]) {
     STAGE_T0();
-    // the words of the rows' costs that the products below do not write (they write MA), read here, ahead
-    // of the products and their sync, whose work covers the round trip:
-    //   fD, lD, cD, far, lar, car, lsg  RD, AREF, LSGN: written by make_rows only
-    //   ff                              per-env model value (DFRIC: constant through the launch)
-    //   fw, lw, w                       WARM: written by euler() and the env code only
-    //   fq, lq, q                       QSM: written by smooth_acc, which ends with a sync of its own
-    //   fsm                             FSM: written by rne and smooth
-    //   jx                              see JxIn
-    struct WarmPre {
-      float fD, ff, far, fw, fq, lD[NLR], lsg[NLR], lar[NLR], lw[NLR], lq[NLR], cD[4], car[4];
-      float fsm[NC], w[NC], q[NC];
-      JxIn jx;
-    } P;
-    {
-      const int r = lane < NFRIC ? lane : 0, i = fric_dof(r);
-      P.fD = L[Ly::RD + r]; P.ff = L[Ly::DFRIC + i]; P.far = L[Ly::AREF + r];
-      P.fw = L[Ly::WARM + i]; P.fq = L[Ly::QSM + i];
-#pragma unroll
-      for (int m = 0; m < NLR; m++) {
-        const int rl = lane + TEAM * m, rc = rl < NLIM ? rl : 0, il = lim_dof(rc);
-        P.lD[m] = L[Ly::RD + R_LIM + rc]; P.lsg[m] = L[Ly::LSGN + rc]; P.lar[m] = L[Ly::AREF + R_LIM + rc];
-        P.lw[m] = L[Ly::WARM + il]; P.lq[m] = L[Ly::QSM + il];
-      }
-      const int slot = lane < NCON ? lane : 0;
-      P.jx = jx_load(L, slot >> 2, slot);
-      for (int e = 0; e < 4; e++) { P.cD[e] = L[Ly::RD + R_CON + 4 * slot + e]; P.car[e] = L[Ly::AREF + R_CON + 4 * slot + e]; }
-#pragma unroll
-      for (int s = 0; s < NC; s++) {
-        const int c = TEAM * s + lane, cc = c < NV ? c : 0;
-        P.fsm[s] = L[Ly::FSM + cc]; P.w[s] = L[Ly::WARM + cc]; P.q[s] = L[Ly::QSM + cc];
-      }
-    }
-    // warm start vs smooth acceleration: J and M products of both in one pass
+    // the words of the rows' costs that the products below do not write (they write MA), read here:
+    //   D, ar, sg of the rows   RD, AREF, LSGN: written by make_rows only
+    //   f                       per-env model value (DFRIC: constant through the launch)
+    //   w                       WARM: written by euler() and the env code only
+    //   q                       QSM: written by smooth_acc, which ends with a sync of its own
+    //   fsm                     FSM: written by rne and smooth
+    //   jx                      see JxIn
+    const WarmPre P(WarmLive<true, true>(L, lane));
+    // J and M products of both starts in one pass
     // (M qacc_smooth = qfrc_smooth by definition: no product needed for the smooth start)
     float sw, ss;
     spatial2(L, lane, Ly::WARM, Ly::QSM, sw, ss);
@@ -3394,276 +3446,222 @@ struct TPhys {
     }
     TSYNC();
     // the feet's spatial motions, broadcast with the full team active (before any lane region)
-    float SL[6], SR[6], SL2[6], SR2[6];
+    float SL[6], SR[6], SL2[6], SR2[6], cwp, csp;
     sp_bcast(sw, SL, SR);
     sp_bcast(ss, SL2, SR2);
     STAGE_MARK(ST_WARM_PRODUCTS);
-    float cwp = 0.0f, csp = 0.0f, gwp = 0.0f;
-    {
-      // branchless (no lane-divergent region: see TL::SINK)
-      const bool fr = lane < NFRIC;
-      const int r = fr ? lane : 0;
-      const float D = P.fD, f = P.ff, ar = P.far;
-      const float jw = P.fw - ar, js = P.fq - ar;
-      cwp += fr ? fric_cost(D, jw, f) : 0.0f;
-      csp += fr ? fric_cost(D, js, f) : 0.0f;
-      L[fr ? Ly::JA + r : TL::SINK + lane] = jw;
-      L[fr ? Ly::JV + r : TL::SINK + TEAM + lane] = js;
-    }
-#pragma unroll
-    for (int m = 0; m < NLR; m++) {
-      const int r = lane + TEAM * m;
-      if (NLIM % TEAM != 0 && m == NLR - 1 && r >= NLIM) continue;
-      const int row = R_LIM + r;
-      const float D = P.lD[m], sg = P.lsg[m], ar = P.lar[m];
-      const float jw = sg * P.lw[m] - ar, js = sg * P.lq[m] - ar;
-      cwp += jw < 0.0f ? 0.5f * D * jw * jw : 0.0f;
-      csp += js < 0.0f ? 0.5f * D * js * js : 0.0f;
-      L[Ly::JA + row] = jw;
-      L[Ly::JV + row] = js;
-    }
-    if (lane < NCON) {
-      float vw[4], vs[4];
-      contact_jx(P.jx, SL, SR, vw);
-      contact_jx(P.jx, SL2, SR2, vs);
-      for (int e = 0; e < 4; e++) {
-        const int row = R_CON + 4 * lane + e;
-        const float D = P.cD[e], ar = P.car[e];
-        const float jw = vw[e] - ar, js = vs[e] - ar;
-        cwp += jw < 0.0f ? 0.5f * D * jw * jw : 0.0f;
-        csp += js < 0.0f ? 0.5f * D * js * js : 0.0f;
-        L[Ly::JA + row] = jw;
-        L[Ly::JV + row] = js;
-      }
-    }
-#pragma unroll
-    for (int s = 0; s < NC; s++) {
-      const int i = TEAM * s + lane;
-      if (NV % TEAM != 0 && s == NC - 1 && i >= NV) continue;
-      gwp += 0.5f * (L[Ly::MA + i] - P.fsm[s]) * (P.w[s] - P.q[s]);
-    }
-    const float gw = tsum(gwp);
-    const float cw = gw + tsum(cwp), cs = tsum(csp);
-    float g0;
-    if (cw < cs) {
-      team_for<NV>(lane, [&](int i) { L[Ly::QACC + i] = L[Ly::WARM + i]; });
-      g0 = gw;
-    } else {
-      team_for<NV>(lane, [&](int i) { L[Ly::QACC + i] = L[Ly::QSM + i]; L[Ly::MA + i] = L[Ly::FSM + i]; });
-      team_for<NROW>(lane, [&](int r) { L[Ly::JA + r] = L[Ly::JV + r]; });
-      g0 = 0.0f;  // gauss(qacc_smooth) = 0.5 (M qs - f).(qs - qs) = 0
-    }
-    TSYNC();
+    warm_rows<true, true>(L, lane, P, SL, SR, SL2, SR2, cwp, csp);
+    bool warm;
+    const float g0 = warm_choose(L, lane, P, cwp, csp, warm);
     STAGE_MARK(ST_WARM_SELECT);
     return g0;
   }
   // Md::iterations Newton steps from the start in QACC / MA / JA (Gauss cost g0 there)
   // pre_dir (latency mode): the first direction is already in TL::XDIR (wave 3's, from the same inputs);
   // used when every team of the wave has one, else the wave computes it (the same values for those teams)
-  static DK void newton(LP L, int lane, float* scratch, int stride, const float (*Mc)[NV], float g0,
-                        bool pre_dir = false) {
+  static DK void newton(LP L, int lane, const float (*Mc)[NV], float g0, bool pre_dir = false) {
     STAGE_T0();
-    (void)scratch;
-    (void)stride;
     for (int newton_it = 0;;) {
-    bool sparse_ok;
-    if (LAT && newton_it == 0 && __ballot(!pre_dir) == 0ull) {
-      team_for<NV>(lane, [&](int i) { L[Ly::SRCH + i] = L[TL::XDIR + i]; });
-      TSYNC();
-      sparse_ok = true;
-    } else {
-      sparse_ok = newton_fused<false>(L, lane, Mc);
-      STAGE_AGAIN(22, sparse_ok = newton_fused<false>(L, lane, Mc));
-    }
-    STAGE_MARK(ST_NEWTON_DIR);
-    if (sparse_ok) {
-      STAGE_MARK(ST_NEWTON_SPARSE);
-    } else {
-      TSYNC();
-      STAGE_COUNT_IF(lane == 0, ST_N_DENSE_FALLBACK, 1ull);
-      newton_dense(L, lane);  // rare: foot/foot contact rows active (dense H)
-      TSYNC();
-    }
-    // the rows' words of the line search that neither the direction nor M.search touch, read here, ahead
-    // of the products and their sync, whose work covers the round trip (the index -> row chains too):
-    //   fD, lD, cD, lsg  RD, LSGN: written by make_rows only
-    //   fja, lja, cja    JA: written by the warm start (and, after a line search, behind a sync of its own)
-    //   ff               per-env model value (DFRIC: constant through the launch)
-    //   jx               see JxIn
-    //   ma, fsm          MA: written by the warm start and after a line search; FSM: by rne and smooth
-    // (the direction writes SRCH, the products GRAD: both are read after the sync)
-    struct SearchPre {
-      float fD, fja, ff, lD[NLR], lja[NLR], lsg[NLR], cD[4], cja[4], ma[NC], fsm[NC];
-      JxIn jx;
-    } SP;
-    {
-      const int slot = lane < NCON ? lane : 0;
-      SP.jx = jx_load(L, slot >> 2, slot);
-      const int r = lane < NFRIC ? lane : 0;
-      SP.fD = L[Ly::RD + r]; SP.fja = L[Ly::JA + r]; SP.ff = L[Ly::DFRIC + fric_dof(r)];
-#pragma unroll
-      for (int m = 0; m < NLR; m++) {
-        const int rl = lane + TEAM * m, rc = rl < NLIM ? rl : 0;
-        SP.lD[m] = L[Ly::RD + R_LIM + rc]; SP.lja[m] = L[Ly::JA + R_LIM + rc]; SP.lsg[m] = L[Ly::LSGN + rc];
-      }
-      for (int e = 0; e < 4; e++) { SP.cD[e] = L[Ly::RD + R_CON + 4 * slot + e]; SP.cja[e] = L[Ly::JA + R_CON + 4 * slot + e]; }
-#pragma unroll
-      for (int s = 0; s < NC; s++) {
-        const int c = TEAM * s + lane, cc = c < NV ? c : 0;
-        SP.ma[s] = L[Ly::MA + cc]; SP.fsm[s] = L[Ly::FSM + cc];
-      }
-    }
-    // J.search and M.search in one pass; rows go straight to registers
-    float sv, sv2;
-    spatial2(L, lane, Ly::SRCH, -1, sv, sv2);
-    {
-      float xs[NC];
-      lane_vec(L, lane, Ly::SRCH, xs);
-      mul_cols(L, lane, Mc, xs, Ly::GRAD);
-    }
-    TSYNC();
-    Rows2 R;
-    {
-      const bool fr = lane < NFRIC;
-      const int r = fr ? lane : 0, i = fric_dof(r);
-      const float D = SP.fD, ja = SP.fja, v = L[Ly::SRCH + i], f = SP.ff;
-      set_fric(R, fr ? D : 1.0f, fr ? ja : 0.0f, fr ? v : 0.0f, fr ? f : 0.0f);
-    }
-#pragma unroll
-    for (int m = 0; m < NLR; m++) {
-      const int r = lane + TEAM * m;
-      const bool ok = r < NLIM;
-      const int rc = ok ? r : 0, i = lim_dof(rc);
-      const float D = SP.lD[m], ja = SP.lja[m], v = SP.lsg[m] * L[Ly::SRCH + i];
-      set_row(R, m, ok ? D : 0.0f, ok ? ja : 0.0f, ok ? v : 0.0f);
-    }
-    {
-      float SL[6], SR[6], v[4];
-      sp_bcast(sv, SL, SR);
-      contact_jx(SP.jx, SL, SR, v);
-      for (int e = 0; e < 4; e++) {
-        const bool ok = lane < NCON;
-        const float D = SP.cD[e], ja = SP.cja[e];
-        set_row(R, NLR + e, ok ? D : 0.0f, ok ? ja : 0.0f, ok ? v[e] : 0.0f);
-      }
-    }
-    float sn = 0.0f, sMa = 0.0f, sf = 0.0f, sMv = 0.0f;
-    LS_DUMP_START(L, lane);
-#pragma unroll
-    for (int s = 0; s < NC; s++) {
-      const int i = TEAM * s + lane;
-      if (NV % TEAM != 0 && s == NC - 1 && i >= NV) continue;
-      const float sv = L[Ly::SRCH + i];
-      sn += sv * sv;
-      sMa += sv * SP.ma[s];
-      sf += sv * SP.fsm[s];
-      sMv += sv * L[Ly::GRAD + i];
-    }
-    LS_DUMP_NORM(L, lane, sn);
-    sn = tsum(sn); sMa = tsum(sMa); sf = tsum(sf); sMv = tsum(sMv);
-    STAGE_MARK(ST_SEARCH_PRODUCTS);
-    const float gtol = Md::tolerance * Md::ls_tolerance * sqrtf(sn) * Md::meaninertia * (float)(NV > 1 ? NV : 1);
-    const float G0 = g0, G1 = sMa - sf, G2 = 0.5f * sMv;
-    auto mk = [&](float alpha, float q0, float q1, float q2) {
-      q1 = tsum(q1) + G1; q2 = tsum(q2) + G2;
-      Pt p;
-      p.alpha = alpha;
-      p.q0p = q0;
-      p.q1 = q1;
-      p.q2 = q2;
-      p.d0 = 2.0f * alpha * q2 + q1;
-      p.d1 = 2.0f * q2;
-      return p;
-    };
-    auto cost = [&](const Pt& p) { return p.alpha * p.alpha * p.q2 + p.alpha * p.q1 + (tsum(p.q0p) + G0); };
-    Pt p0;
-    {
-      float q0 = 0, q1 = 0, q2 = 0;
-      quad2(R, 0.0f, q0, q1, q2);
-      LS_DUMP_QUAD(L, lane, q0, q1, q2, G0, G1, G2, gtol, sn);
-      p0 = mk(0.0f, q0, q1, q2);
-    }
-    Pt lo;
-    {
-      // (as the loop's steps: alpha - d0 v_rcp(d1); written as a division this one, at alpha = 0, compiled
-      // to the correctly rounded sequence with two MODE register writes)
-      const float a1 = p0.alpha - p0.d0 * frcp(p0.d1);
-      float q0 = 0, q1 = 0, q2 = 0;
-      quad2(R, a1, q0, q1, q2);
-      lo = mk(a1, q0, q1, q2);
-    }
-    Pt hi;
-    if (lo.d0 < p0.d0) { hi = p0; } else { hi = lo; lo = p0; }
-    bool swap = true;
-    // fp32 termination floor: a bracket end whose slope is below 1e-6 of the starting slope is at the
-    // minimum to fp32 resolution; MJX's gtol (tolerance * ls_tolerance * |search| ...) alone is far
-    // below fp32 noise, so fp32 iterations would keep swapping on rounding
-    const float gtol_ls = fmaxf(gtol, LS_SLOPE_FLOOR * fabsf(p0.d0));
-    STAGE_PROF_ONLY(int its = 0;)  // (iterations this team needed, against those its wave ran)
-    for (int it = 0; it < Md::ls_iterations; it++) {
-      bool done = !swap;
-      done = done || ((lo.d0 < 0.0f) && (lo.d0 > -gtol_ls));
-      done = done || ((hi.d0 > 0.0f) && (hi.d0 < gtol_ls));
-      if (done) break;
-      STAGE_PROF_ONLY(its = it + 1;)
-      STAGE_COUNT_WAVE0(ST_N_LS_WAVE_ITERS, 1ull);
-      const float al = lo.alpha - lo.d0 / lo.d1, ah = hi.alpha - hi.d0 / hi.d1, am = 0.5f * (lo.alpha + hi.alpha);
-      float a0 = 0, a1 = 0, a2 = 0, b0 = 0, b1 = 0, b2 = 0, c0 = 0, c1 = 0, c2 = 0;
-      if constexpr (LS_PAIRS) {
-        f2v p0 = {0.0f, 0.0f}, p1 = {0.0f, 0.0f}, p2 = {0.0f, 0.0f};
-        quad2_pair(R, f2v{al, ah}, p0, p1, p2);
-        a0 = p0.x; b0 = p0.y; a1 = p1.x; b1 = p1.y; a2 = p2.x; b2 = p2.y;
+      bool sparse_ok;
+      if (LAT && newton_it == 0 && __ballot(!pre_dir) == 0ull) {
+        team_for<NV>(lane, [&](int i) { L[Ly::SRCH + i] = L[TL::XDIR + i]; });
+        TSYNC();
+        sparse_ok = true;
       } else {
-        quad2(R, al, a0, a1, a2);
-        quad2(R, ah, b0, b1, b2);
+        sparse_ok = newton_fused<false>(L, lane, Mc);
+        STAGE_AGAIN(22, sparse_ok = newton_fused<false>(L, lane, Mc));
       }
-      quad2(R, am, c0, c1, c2);
-      const Pt lo_next = mk(al, a0, a1, a2), hi_next = mk(ah, b0, b1, b2), mid = mk(am, c0, c1, c2);
-      const bool s1 = (lo.d0 > 0.0f) || (lo.d0 < lo_next.d0);
-      if (s1) lo = lo_next;
-      const bool s2 = (mid.d0 < 0.0f) && (lo.d0 < mid.d0);
-      if (s2) lo = mid;
-      const bool s3 = (hi.d0 < 0.0f) || (hi.d0 > hi_next.d0);
-      if (s3) hi = hi_next;
-      const bool s4 = (mid.d0 > 0.0f) && (hi.d0 > mid.d0);
-      if (s4) hi = mid;
-      swap = s1 || s2 || s3 || s4;
-    }
-    STAGE_PROF_ONLY(if (threadIdx.x < 64 && (lane & 15) == 0) {
-      STAGE_COUNT(ST_N_LS_TEAM_ITERS, (unsigned long long)its);
-      STAGE_COUNT(ST_N_LS_SEARCHES, 1ull);
-    })
-    const float lo_cost = cost(lo), hi_cost = cost(hi), p0_cost = cost(p0);
-    const bool improved = (lo_cost < p0_cost) || (hi_cost < p0_cost);
-    const float alpha = lo_cost < hi_cost ? lo.alpha : hi.alpha;
-    if (improved)
-      team_for<NV>(lane, [&](int i) { L[Ly::QACC + i] += L[Ly::SRCH + i] * alpha; });
-    TSYNC();
-    STAGE_MARK(ST_LINESEARCH);
-    if constexpr (Md::iterations <= 1) {
-      break;
-    } else {
-      // next Newton step from the new point (mjx solver.solve loop): M.qacc and J.qacc - aref move
-      // along the search direction; stop on the iteration count or a cost improvement below
-      // tolerance (the gradient-norm test is not repeated here: at that point the next step's
-      // change is below fp32 resolution)
-      if (++newton_it >= Md::iterations) break;
-      const float a = improved ? alpha : 0.0f;
-      const float cnew = improved ? (lo_cost < hi_cost ? lo_cost : hi_cost) : p0_cost;
-      g0 = G0 + a * G1 + a * a * G2;  // gauss at the new point
-      team_for<NV>(lane, [&](int i) { L[Ly::MA + i] += a * L[Ly::GRAD + i]; });  // GRAD = M.search
-      if (lane < NFRIC) L[Ly::JA + lane] = R.fja + a * R.fv;
+      STAGE_MARK(ST_NEWTON_DIR);
+      if (sparse_ok) {
+        STAGE_MARK(ST_NEWTON_SPARSE);
+      } else {
+        TSYNC();
+        STAGE_COUNT_IF(lane == 0, ST_N_DENSE_FALLBACK, 1ull);
+        newton_dense(L, lane);  // rare: foot/foot contact rows active (dense H)
+        TSYNC();
+      }
+      // the rows' words of the line search that neither the direction nor M.search touch, read here, ahead
+      // of the products and their sync, whose work covers the round trip (the index -> row chains too):
+      //   fD, lD, cD, lsg  RD, LSGN: written by make_rows only
+      //   fja, lja, cja    JA: written by the warm start (and, after a line search, behind a sync of its own)
+      //   ff               per-env model value (DFRIC: constant through the launch)
+      //   jx               see JxIn
+      //   ma, fsm          MA: written by the warm start and after a line search; FSM: by rne and smooth
+      // (the direction writes SRCH, the products GRAD: both are read after the sync)
+      struct SearchPre {
+        float fD, fja, ff, lD[NLR], lja[NLR], lsg[NLR], cD[4], cja[4], ma[NC], fsm[NC];
+        JxIn jx;
+      } SP;
+      {
+        const int slot = lane < NCON ? lane : 0;
+        SP.jx = jx_load(L, slot >> 2, slot);
+        const int r = lane < NFRIC ? lane : 0;
+        SP.fD = L[Ly::RD + r]; SP.fja = L[Ly::JA + r]; SP.ff = L[Ly::DFRIC + fric_dof(r)];
+#pragma unroll
+        for (int m = 0; m < NLR; m++) {
+          const int rl = lane + TEAM * m, rc = rl < NLIM ? rl : 0;
+          SP.lD[m] = L[Ly::RD + R_LIM + rc]; SP.lja[m] = L[Ly::JA + R_LIM + rc]; SP.lsg[m] = L[Ly::LSGN + rc];
+        }
+        for (int e = 0; e < 4; e++) {
+          SP.cD[e] = L[Ly::RD + R_CON + 4 * slot + e]; SP.cja[e] = L[Ly::JA + R_CON + 4 * slot + e];
+        }
+#pragma unroll
+        for (int s = 0; s < NC; s++) {
+          const int c = TEAM * s + lane, cc = c < NV ? c : 0;
+          SP.ma[s] = L[Ly::MA + cc]; SP.fsm[s] = L[Ly::FSM + cc];
+        }
+      }
+      // J.search and M.search in one pass; rows go straight to registers
+      float sv, sv2;
+      spatial2(L, lane, Ly::SRCH, -1, sv, sv2);
+      {
+        float xs[NC];
+        lane_vec(L, lane, Ly::SRCH, xs);
+        mul_cols(L, lane, Mc, xs, Ly::GRAD);
+      }
+      TSYNC();
+      Rows2 R;
+      {
+        const bool fr = lane < NFRIC;
+        const int r = fr ? lane : 0, i = fric_dof(r);
+        const float D = SP.fD, ja = SP.fja, v = L[Ly::SRCH + i], f = SP.ff;
+        set_fric(R, fr ? D : 1.0f, fr ? ja : 0.0f, fr ? v : 0.0f, fr ? f : 0.0f);
+      }
 #pragma unroll
       for (int m = 0; m < NLR; m++) {
         const int r = lane + TEAM * m;
-        if (r < NLIM) L[Ly::JA + R_LIM + r] = R.ja[m] + a * R.v[m];
+        const bool ok = r < NLIM;
+        const int rc = ok ? r : 0, i = lim_dof(rc);
+        const float D = SP.lD[m], ja = SP.lja[m], v = SP.lsg[m] * L[Ly::SRCH + i];
+        set_row(R, m, ok ? D : 0.0f, ok ? ja : 0.0f, ok ? v : 0.0f);
       }
-      if (lane < NCON)
-        for (int e = 0; e < 4; e++) L[Ly::JA + R_CON + 4 * lane + e] = R.ja[NLR + e] + a * R.v[NLR + e];
+      {
+        float SL[6], SR[6], v[4];
+        sp_bcast(sv, SL, SR);
+        contact_jx(SP.jx, SL, SR, v);
+        for (int e = 0; e < 4; e++) {
+          const bool ok = lane < NCON;
+          const float D = SP.cD[e], ja = SP.cja[e];
+          set_row(R, NLR + e, ok ? D : 0.0f, ok ? ja : 0.0f, ok ? v[e] : 0.0f);
+        }
+      }
+      float sn = 0.0f, sMa = 0.0f, sf = 0.0f, sMv = 0.0f;
+      LS_DUMP_START(L, lane);
+#pragma unroll
+      for (int s = 0; s < NC; s++) {
+        const int i = TEAM * s + lane;
+        if (NV % TEAM != 0 && s == NC - 1 && i >= NV) continue;
+        const float sv = L[Ly::SRCH + i];
+        sn += sv * sv;
+        sMa += sv * SP.ma[s];
+        sf += sv * SP.fsm[s];
+        sMv += sv * L[Ly::GRAD + i];
+      }
+      LS_DUMP_NORM(L, lane, sn);
+      sn = tsum(sn); sMa = tsum(sMa); sf = tsum(sf); sMv = tsum(sMv);
+      STAGE_MARK(ST_SEARCH_PRODUCTS);
+      const float gtol = Md::tolerance * Md::ls_tolerance * sqrtf(sn) * Md::meaninertia * (float)(NV > 1 ? NV : 1);
+      const float G0 = g0, G1 = sMa - sf, G2 = 0.5f * sMv;
+      auto mk = [&](float alpha, float q0, float q1, float q2) {
+        q1 = tsum(q1) + G1; q2 = tsum(q2) + G2;
+        Pt p;
+        p.alpha = alpha;
+        p.q0p = q0;
+        p.q1 = q1;
+        p.q2 = q2;
+        p.d0 = 2.0f * alpha * q2 + q1;
+        p.d1 = 2.0f * q2;
+        return p;
+      };
+      auto cost = [&](const Pt& p) { return p.alpha * p.alpha * p.q2 + p.alpha * p.q1 + (tsum(p.q0p) + G0); };
+      Pt p0;
+      {
+        float q0 = 0, q1 = 0, q2 = 0;
+        quad2(R, 0.0f, q0, q1, q2);
+        LS_DUMP_QUAD(L, lane, q0, q1, q2, G0, G1, G2, gtol, sn);
+        p0 = mk(0.0f, q0, q1, q2);
+      }
+      Pt lo;
+      {
+        // (as the loop's steps: alpha - d0 v_rcp(d1); written as a division this one, at alpha = 0, compiled
+        // to the correctly rounded sequence with two MODE register writes)
+        const float a1 = p0.alpha - p0.d0 * frcp(p0.d1);
+        float q0 = 0, q1 = 0, q2 = 0;
+        quad2(R, a1, q0, q1, q2);
+        lo = mk(a1, q0, q1, q2);
+      }
+      Pt hi;
+      if (lo.d0 < p0.d0) { hi = p0; } else { hi = lo; lo = p0; }
+      bool swap = true;
+      // fp32 termination floor: a bracket end whose slope is below 1e-6 of the starting slope is at the
+      // minimum to fp32 resolution; MJX's gtol (tolerance * ls_tolerance * |search| ...) alone is far
+      // below fp32 noise, so fp32 iterations would keep swapping on rounding
+      const float gtol_ls = fmaxf(gtol, LS_SLOPE_FLOOR * fabsf(p0.d0));
+      STAGE_PROF_ONLY(int its = 0;)  // (iterations this team needed, against those its wave ran)
+      for (int it = 0; it < Md::ls_iterations; it++) {
+        bool done = !swap;
+        done = done || ((lo.d0 < 0.0f) && (lo.d0 > -gtol_ls));
+        done = done || ((hi.d0 > 0.0f) && (hi.d0 < gtol_ls));
+        if (done) break;
+        STAGE_PROF_ONLY(its = it + 1;)
+        STAGE_COUNT_WAVE0(ST_N_LS_WAVE_ITERS, 1ull);
+        const float al = lo.alpha - lo.d0 / lo.d1, ah = hi.alpha - hi.d0 / hi.d1, am = 0.5f * (lo.alpha + hi.alpha);
+        float a0 = 0, a1 = 0, a2 = 0, b0 = 0, b1 = 0, b2 = 0, c0 = 0, c1 = 0, c2 = 0;
+        if constexpr (LS_PAIRS) {
+          f2v p0 = {0.0f, 0.0f}, p1 = {0.0f, 0.0f}, p2 = {0.0f, 0.0f};
+          quad2_pair(R, f2v{al, ah}, p0, p1, p2);
+          a0 = p0.x; b0 = p0.y; a1 = p1.x; b1 = p1.y; a2 = p2.x; b2 = p2.y;
+        } else {
+          quad2(R, al, a0, a1, a2);
+          quad2(R, ah, b0, b1, b2);
+        }
+        quad2(R, am, c0, c1, c2);
+        const Pt lo_next = mk(al, a0, a1, a2), hi_next = mk(ah, b0, b1, b2), mid = mk(am, c0, c1, c2);
+        const bool s1 = (lo.d0 > 0.0f) || (lo.d0 < lo_next.d0);
+        if (s1) lo = lo_next;
+        const bool s2 = (mid.d0 < 0.0f) && (lo.d0 < mid.d0);
+        if (s2) lo = mid;
+        const bool s3 = (hi.d0 < 0.0f) || (hi.d0 > hi_next.d0);
+        if (s3) hi = hi_next;
+        const bool s4 = (mid.d0 > 0.0f) && (hi.d0 > mid.d0);
+        if (s4) hi = mid;
+        swap = s1 || s2 || s3 || s4;
+      }
+      STAGE_PROF_ONLY(if (threadIdx.x < 64 && (lane & 15) == 0) {
+        STAGE_COUNT(ST_N_LS_TEAM_ITERS, (unsigned long long)its);
+        STAGE_COUNT(ST_N_LS_SEARCHES, 1ull);
+      })
+      const float lo_cost = cost(lo), hi_cost = cost(hi), p0_cost = cost(p0);
+      const bool improved = (lo_cost < p0_cost) || (hi_cost < p0_cost);
+      const float alpha = lo_cost < hi_cost ? lo.alpha : hi.alpha;
+      if (improved)
+        team_for<NV>(lane, [&](int i) { L[Ly::QACC + i] += L[Ly::SRCH + i] * alpha; });
       TSYNC();
-      const float scale = 1.0f / (Md::meaninertia * (float)(NV > 1 ? NV : 1));
-      if (scale * (p0_cost - cnew) < Md::tolerance) break;
-    }
+      STAGE_MARK(ST_LINESEARCH);
+      if constexpr (Md::iterations <= 1) {
+        break;
+      } else {
+        // next Newton step from the new point (mjx solver.solve loop): M.qacc and J.qacc - aref move
+        // along the search direction; stop on the iteration count or a cost improvement below
+        // tolerance (the gradient-norm test is not repeated here: at that point the next step's
+        // change is below fp32 resolution)
+        if (++newton_it >= Md::iterations) break;
+        const float a = improved ? alpha : 0.0f;
+        const float cnew = improved ? (lo_cost < hi_cost ? lo_cost : hi_cost) : p0_cost;
+        g0 = G0 + a * G1 + a * a * G2;  // gauss at the new point
+        team_for<NV>(lane, [&](int i) { L[Ly::MA + i] += a * L[Ly::GRAD + i]; });  // GRAD = M.search
+        if (lane < NFRIC) L[Ly::JA + lane] = R.fja + a * R.fv;
+#pragma unroll
+        for (int m = 0; m < NLR; m++) {
+          const int r = lane + TEAM * m;
+          if (r < NLIM) L[Ly::JA + R_LIM + r] = R.ja[m] + a * R.v[m];
+        }
+        if (lane < NCON)
+          for (int e = 0; e < 4; e++) L[Ly::JA + R_CON + 4 * lane + e] = R.ja[NLR + e] + a * R.v[NLR + e];
+        TSYNC();
+        const float scale = 1.0f / (Md::meaninertia * (float)(NV > 1 ? NV : 1));
+        if (scale * (p0_cost - cnew) < Md::tolerance) break;
+      }
     }
   }
 
@@ -3769,8 +3767,17 @@ struct TPhys {
     TSYNC();
   }
 
-  static DK void step(LP L, int lane, bool integrate, bool want_out, float* aux, int aux_stride, float* scratch,
-                      int sstride, const float* hf) {
+  // the end of a substep: integrate, or (forward only) leave qacc as the next call's warm start
+  static DK void end_substep(LP L, int lane, bool integrate) {
+    if (integrate) {
+      euler(L, lane);
+    } else {
+      team_for<NV>(lane, [&](int i) { L[Ly::WARM + i] = L[Ly::QACC + i]; });
+      TSYNC();
+    }
+  }
+
+  static DK void step(LP L, int lane, bool integrate, bool want_out, float* aux, int aux_stride, const float* hf) {
     STAGE_T0();
     // each stage's prologue (the words it may read before the stage ahead of it has finished) is issued ahead
     // of that stage, whose work then covers the round trip
@@ -3811,8 +3818,8 @@ struct TPhys {
       smooth_acc(L, lane, Mc);
       STAGE_AGAIN(4, smooth_acc(L, lane, Mc));
       STAGE_MARK(ST_SMOOTH_ACC);
-      solve(L, lane, scratch, sstride, Mc);
-      STAGE_AGAIN(5, solve(L, lane, scratch, sstride, Mc));  // (reads qacc_warmstart / qacc_smooth, not qacc)
+      solve(L, lane, Mc);
+      STAGE_AGAIN(5, solve(L, lane, Mc));  // (reads qacc_warmstart / qacc_smooth, not qacc)
     }
     STAGE_MARK(ST_SOLVE);
     if (want_out) {
@@ -3821,12 +3828,7 @@ struct TPhys {
         if (lane == 0) Ph::write_aux(L, aux, aux_stride);
       }
     }
-    if (integrate) {
-      euler(L, lane);
-    } else {
-      team_for<NV>(lane, [&](int i) { L[Ly::WARM + i] = L[Ly::QACC + i]; });
-      TSYNC();
-    }
+    end_substep(L, lane, integrate);
     STAGE_MARK(ST_SENSORS_EULER);
   }
 
@@ -3879,6 +3881,20 @@ struct TPhys {
     extern __shared__ LDS_ALIGNED float lds_dyn[];
     return ((lds_int*)(lds_dyn + TL::EV))[4 * (EV_TIMEOUT + TL::NEV_G * g)] != 0;
   }
+  // the Newton direction at qacc_warmstart into TL::XDIR, speculatively, with its ok word behind it
+  // (the caller has waited for M's columns and EV_WA, and signals EV_DIR)
+  static DK void spec_dir(LP L, int lane, const float (*Mc)[NV]) {
+    const bool ok = newton_fused<false, TL::XDIR>(L, lane, Mc);
+    if (lane == 0) L[TL::XDIR + NV] = ok ? 1.0f : 0.0f;
+    TSYNC();
+  }
+  // is that direction newton()'s first? Only if every team of the wave starts from qacc_warmstart (the
+  // common case: the direction was computed there meanwhile); otherwise the wave computes its own (no wait)
+  static DK bool take_dir(LP L, bool warm, int s) {
+    if (__ballot(!warm) != 0ull) return false;
+    ev_wait(EV_DIR, s + 1);
+    return L[TL::XDIR + NV] != 0.0f;
+  }
   // wave 0, substep s: kinematics and com_pos (everything else waits for them), rne's velocities
   // (the contact rows need the feet's), then the rest of rne and the actuation (qfrc_smooth)
   static DK void lat_r0(LP L, int lane, int s) {
@@ -3899,7 +3915,7 @@ struct TPhys {
   // wave 1: composite inertias and M (crb) while wave 0 finishes rne; M's register columns and the warm
   // start's products of qacc_warmstart while wave 3 factors M and solves for qacc_smooth; then the rest
   // of the warm start, the Newton solve, sensors, Euler
-  static DK void lat_r1(LP L, int lane, int s, bool integrate, bool want_out, float* scratch, int sstride) {
+  static DK void lat_r1(LP L, int lane, int s, bool integrate, bool want_out) {
     ev_wait(EV_KIN, s + 1);
     LAT_T(10, s);
     subtree_sums<2>(L, lane);
@@ -3922,24 +3938,13 @@ struct TPhys {
       bool warm;
       const float g0 = warm_start_b(L, lane, cwp, warm);
       LAT_T(16, s);
-      // every team starts from qacc_warmstart (the common case): wave 3 has computed the Newton direction
-      // there meanwhile; otherwise this wave computes it (no wait)
-      bool pre = false;
-      if (__ballot(!warm) == 0ull) {
-        ev_wait(EV_DIR, s + 1);
-        pre = L[TL::XDIR + NV] != 0.0f;
-      }
+      const bool pre = take_dir(L, warm, s);  // (wave 3's direction)
       LAT_T(19, s);
-      newton(L, lane, scratch, sstride, Mc, g0, pre);
+      newton(L, lane, Mc, g0, pre);
       LAT_T(17, s);
     }
     if (want_out) sensors(L, lane);
-    if (integrate) {
-      euler(L, lane);
-    } else {
-      team_for<NV>(lane, [&](int i) { L[Ly::WARM + i] = L[Ly::QACC + i]; });
-      TSYNC();
-    }
+    end_substep(L, lane, integrate);
     ev_signal(EV_EULER, s + 1);
     LAT_T(18, s);
   }
@@ -3973,9 +3978,7 @@ struct TPhys {
     // everywhere in the wave): the rows' values there and M qacc_warmstart come from wave 1's warm start
     ev_wait(EV_WA, s + 1);
     LAT_T(34, s);
-    const bool ok = newton_fused<false, TL::XDIR>(L, lane, Mc);
-    if (lane == 0) L[TL::XDIR + NV] = ok ? 1.0f : 0.0f;
-    TSYNC();
+    spec_dir(L, lane, Mc);
     ev_signal(EV_DIR, s + 1);
     LAT_T(35, s);
   }
@@ -4016,13 +4019,11 @@ struct TPhys {
     load_cols(L, lane, Mc);
     ev_wait(EV_WA, s + 1);
     LAT2_T(7, s);
-    const bool ok = newton_fused<false, TL::XDIR>(L, lane, Mc);
-    if (lane == 0) L[TL::XDIR + NV] = ok ? 1.0f : 0.0f;
-    TSYNC();
+    spec_dir(L, lane, Mc);
     ev_signal(EV_DIR, s + 1);
     LAT2_T(8, s);
   }
-  static DK void lat2_b(LP L, int lane, int s, bool integrate, bool want_out, float* scratch, int sstride) {
+  static DK void lat2_b(LP L, int lane, int s, bool integrate, bool want_out) {
     ev_wait(EV_KIN, s + 1);
     LAT2_T(10, s);
     subtree_sums<2>(L, lane);
@@ -4053,22 +4054,13 @@ struct TPhys {
       bool warm;
       const float g0 = warm_start_b(L, lane, cwp, warm);
       LAT2_T(19, s);
-      bool pre = false;
-      if (__ballot(!warm) == 0ull) {
-        ev_wait(EV_DIR, s + 1);
-        pre = L[TL::XDIR + NV] != 0.0f;
-      }
+      const bool pre = take_dir(L, warm, s);
       LAT2_T(20, s);
-      newton(L, lane, scratch, sstride, Mc, g0, pre);
+      newton(L, lane, Mc, g0, pre);
       LAT2_T(21, s);
     }
     if (want_out) sensors(L, lane);
-    if (integrate) {
-      euler(L, lane);
-    } else {
-      team_for<NV>(lane, [&](int i) { L[Ly::WARM + i] = L[Ly::QACC + i]; });
-      TSYNC();
-    }
+    end_substep(L, lane, integrate);
     LAT2_T(22, s);
     ev_signal(EV_EULER, s + 1);
   }

@@ -213,7 +213,6 @@ class Joystick(OpenDuckMiniV2Env):
         check(self._lib.duck_create(C.byref(self._desc.desc), C.byref(self._cfg_struct), C.byref(self._ref_struct),
                                     dev, C.byref(handle)), self._lib)
         self._sim = handle
-        self._scratch = None
         check(self._lib.duck_set_step_mode(self._sim, STEP_MODES[self._step_mode]), self._lib)
 
     def set_step_mode(self, mode: str) -> None:
@@ -344,15 +343,9 @@ class Joystick(OpenDuckMiniV2Env):
         check(self._lib.duck_step(self._sim, n, state.fstate.data_ptr(), state.istate.data_ptr(),
                               self.dr.data_ptr() if self.dr is not None else None, action.data_ptr(),
                               state.obs["state"].data_ptr(), state.obs["privileged_state"].data_ptr(),
-                              state.reward.data_ptr(), state.done.data_ptr(), self._scratch_ptr(), self._stream()),
+                              state.reward.data_ptr(), state.done.data_ptr(), self._stream()),
               self._lib)
         return state
-
-    def _scratch_ptr(self):
-        if self._scratch is None:
-            nv = self._mj_model.nv
-            self._scratch = torch.zeros(self.num_envs * nv * nv, dtype=torch.float32, device=self.device)
-        return self._scratch.data_ptr()
 
     # physics-level entry: mjx_env.step(model, data, ctrl, n_substeps) (joystick.py:420)
     def physics_step(self, qpos: torch.Tensor, qvel: torch.Tensor, qacc_warmstart: torch.Tensor, ctrl: torch.Tensor,
@@ -362,11 +355,10 @@ class Joystick(OpenDuckMiniV2Env):
         for t in (qpos, qvel, qacc_warmstart, ctrl):
             if not t.is_contiguous() or t.dtype != torch.float32 or t.device != self.device or t.shape[1] != n:
                 raise DuckError("physics_step expects contiguous float32 SoA tensors on the env device")
-        scratch = torch.zeros(n * self._mj_model.nv ** 2, dtype=torch.float32, device=self.device)
         check(self._lib.duck_physics_step(self._sim, n, qpos.data_ptr(), qvel.data_ptr(), qacc_warmstart.data_ptr(),
                                       ctrl.data_ptr(), self.dr.data_ptr() if self.dr is not None else None,
-                                      int(n_substeps), aux.data_ptr() if aux is not None else None,
-                                      scratch.data_ptr(), self._stream()), self._lib)
+                                      int(n_substeps), aux.data_ptr() if aux is not None else None, self._stream()),
+              self._lib)
 
     def aux_size(self) -> int:
         return int(self._lib.duck_aux_size(self._sim))

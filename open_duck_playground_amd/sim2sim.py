@@ -405,7 +405,6 @@ class FleetInfer:
         z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)  # noqa: E731
         self.qpos, self.qvel = z(m.nq, n), z(m.nv, n)
         self.warm, self.ctrl, self.aux = z(m.nv, n), z(nu, n), z(naux, n)
-        self._scratch = z(n * m.nv * m.nv)
         self.fields = ctl_fields(nu)
         self.ctl, self.obs, self.action = z(n, HEADERS.value(f"DUCK_FLEET_CTL_SIZE({nu})")), z(n, self.obs_size), z(n, nu)
         self.acc, self.alive = z(n, HEADERS.consts["DUCK_FLEET_ACC_SIZE"]), torch.ones(n, dtype=torch.float32, device=dev)
@@ -499,7 +498,7 @@ class FleetInfer:
         self._check(L.duck_physics_step(self._sim, self.num_robots, self.qpos.data_ptr(), self.qvel.data_ptr(),
                                         self.warm.data_ptr(), self.ctrl.data_ptr(),
                                         None if self.dr is None else self.dr.data_ptr(), int(n_substeps),
-                                        self.aux.data_ptr(), self._scratch.data_ptr(), self._stream()), L)
+                                        self.aux.data_ptr(), self._stream()), L)
 
     def _launch(self, name: str, *args, lead=()):
         """A fleet entry of the model's library: the descriptor (then ``lead``) and N in front, tensors as their
