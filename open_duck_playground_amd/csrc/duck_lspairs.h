@@ -45,3 +45,20 @@ constexpr bool ls_pairs() {
   return !(Md::FLOOR_TYPE == 1 && Md::NLIM <= 16);
 #endif
 }
+
+// The scenes whose fused warm start (duck_team.h warm_start: the throughput kernel and physics_kernel) runs
+// its two starts' chains, qacc_warmstart and qacc_smooth, as packed pairs (warm_rows_pair, spatial2_pair).
+// Neither form moves a bit; a scene whose measured interval falls below its parent's keeps the scalar form
+// (warm_rows_both's own statements). Every scene takes the pairs: against the scalar form with the same
+// stores, C2 23.07-23.12 for 22.93-22.96 M env-steps/s (profiles/r15_warm_pairs_ab.txt, section 1).
+// -DDUCK_SCALAR_TWINS (the scalar_twins test library of __graft_entry__.build()): no scene.
+// -DDUCK_SCALAR_WARM: no scene either, beside the paired line search; the library of that A/B, built by hand as
+// native.build(defines=["DUCK_SCALAR_WARM"], out=".../libduck_sw.so") and timed with tools/gpu_ab_libs.sh.
+template <class Md>
+constexpr bool warm_pairs() {
+#if defined(DUCK_SCALAR_TWINS) || defined(DUCK_SCALAR_WARM)
+  return false;
+#else
+  return true;
+#endif
+}

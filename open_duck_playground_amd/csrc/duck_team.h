@@ -3047,6 +3047,7 @@ struct TPhys {
   // the slot's words contact_jx reads: the pair's geoms and friction (words of the model table, never
   // written after the launch's table copy) and the contact's arm and frame (CR, CFR: written by the
   // collision stage only), so a solver stage may load them ahead of the sync that precedes its use of them
+  static constexpr bool JX_GUARDED = LAT == 2 && Md::FLOOR_TYPE == 1 && Md::NLIM > 16;  // (contact_jx)
   struct JxIn {
     int s1, s2;
     float mu, r[3], fr[9];
@@ -3071,9 +3072,36 @@ struct TPhys {
     const int s1 = J.s1, s2 = J.s2;
     const float mu = J.mu;
     const float r[3] = {J.r[0], J.r[1], J.r[2]};
-    float v[3] = {0.0f, 0.0f, 0.0f}, t[3];
-    if (s2 != 0) { Ph::contact_vel(s2 == 1 ? SL : SR, r, t); v[0] += t[0]; v[1] += t[1]; v[2] += t[2]; }
-    if (s1 != 0) { Ph::contact_vel(s1 == 1 ? SL : SR, r, t); v[0] -= t[0]; v[1] -= t[1]; v[2] -= t[2]; }
+    // Straight-line: both geoms' point velocities on every lane, the foot's motion selected per component
+    // (s = 1 left, else right) and a geom of the world (s = 0) dropped by a select of the sum. As two blocks
+    // guarded by s2 != 0 and s1 != 0 the statements were the same but stood in exec-masked regions of their own
+    // (four in the fused warm start), which nothing could be scheduled across. The s1 term keeps the form
+    // v - (Sp + w x r): the compiler pushes the negation into the cross product there, which then rounds its
+    // other product (profiles/r15_contraction_points.txt), so it is not the s2 term negated.
+    // JX_GUARDED: one kernel keeps the two guarded blocks, the parent's text, the same values (the step kernels
+    // are compared word for word on states that take both geoms' terms, tests/test_gpu_warm_pairs.py, and over
+    // episodes, tests/test_gpu_env.py::test_latency_mode_matches_throughput_mode). It is the paired latency kernel
+    // of a height-field scene with backlash, whose source then is the parent's throughout: straight-line it ran
+    // below its parent's interval, C5 at 2,048 envs 5.852-5.853 against 5.862-5.876 M env-steps/s, with the blocks
+    // 5.858-5.875 in the same alternating runs (profiles/r15_warm_pairs_ab.txt, section 3). Its register
+    // counts are equal either way; why the blocks suit it is not known.
+    float v[3] = {0.0f, 0.0f, 0.0f};
+    if constexpr (!JX_GUARDED) {
+      float S2[6], S1[6], t2[3], t1[3];
+#pragma unroll
+      for (int k = 0; k < 6; k++) { S2[k] = s2 == 1 ? SL[k] : SR[k]; S1[k] = s1 == 1 ? SL[k] : SR[k]; }
+      Ph::contact_vel(S2, r, t2);
+      Ph::contact_vel(S1, r, t1);
+#pragma unroll
+      for (int a = 0; a < 3; a++) {
+        const float va = s2 != 0 ? t2[a] : 0.0f, vb = va - t1[a];
+        v[a] = s1 != 0 ? vb : va;
+      }
+    } else {
+      float t[3];
+      if (s2 != 0) { Ph::contact_vel(s2 == 1 ? SL : SR, r, t); v[0] += t[0]; v[1] += t[1]; v[2] += t[2]; }
+      if (s1 != 0) { Ph::contact_vel(s1 == 1 ? SL : SR, r, t); v[0] -= t[0]; v[1] -= t[1]; v[2] -= t[2]; }
+    }
     float jr[3];
     for (int q = 0; q < 3; q++)
       jr[q] = J.fr[3 * q] * v[0] + J.fr[3 * q + 1] * v[1] + J.fr[3 * q + 2] * v[2];
@@ -3142,6 +3170,48 @@ struct TPhys {
       so = s;
       so2 = s2;
     }
+  }
+
+  // spatial2 of X and X2 as one pair (.x of X, .y of X2): per chain position one packed FMA with the cdof
+  // word splat, the unit free-joint rows selects per half and a packed add; each half is spatial2's
+  // operation at that position (profiles/r15_contraction_points.txt). A position's two words, X + ic and
+  // X2 + ic, come from one two-address load into adjacent registers.
+  static DK void spatial2_pair(LP L, int lane, int X, int X2, float& so, float& so2) {
+#pragma clang fp contract(off)
+    f2v s = {0.0f, 0.0f};
+    if (lane < 12) {
+      int lo = lane;
+      asm volatile("" : "+v"(lo));  // (as in spatial2)
+      const bool left = lo < 6;
+      const int k = left ? lo : lo - 6;
+      float cvs[Md::MAXCHAIN];
+      f2v xs[Md::MAXCHAIN];
+#pragma unroll
+      for (int c = 0; c < Md::MAXCHAIN; c++) {
+        const int iL = Md::chain[Md::LFOOT_BODY][c], iR = Md::chain[Md::RFOOT_BODY][c];
+        cvs[c] = 0.0f;
+        xs[c] = f2v{0.0f, 0.0f};
+        if (iL < 0 && iR < 0) continue;
+        const bool unit = FREE0 && iL == iR && iL >= 0 && iL < 3;
+        const int ic = unit ? iL : (left ? (iL >= 0 ? iL : 0) : (iR >= 0 ? iR : 0));
+        if (!unit) cvs[c] = L[Ly::CDOF + 6 * ic + k];
+        xs[c] = f2v{L[X + ic], L[X2 + ic]};
+      }
+#pragma unroll
+      for (int c = 0; c < Md::MAXCHAIN; c++) {
+        const int iL = Md::chain[Md::LFOOT_BODY][c], iR = Md::chain[Md::RFOOT_BODY][c];
+        if (iL < 0 && iR < 0) continue;
+        const bool ok = left ? iL >= 0 : iR >= 0;
+        if (FREE0 && iL == iR && iL >= 0 && iL < 3) {
+          const bool on = k == 3 + iL;
+          s += f2v{on ? xs[c].x : 0.0f, on ? xs[c].y : 0.0f};
+          continue;
+        }
+        s = pfma(sp2(ok ? cvs[c] : 0.0f), xs[c], s);
+      }
+    }
+    so = s.x;
+    so2 = s.y;
   }
 
   // SL[k] = component k of the left foot's motion (lane k), SR[k] the right foot's (lane 6 + k)
@@ -3257,7 +3327,8 @@ struct TPhys {
     newton(L, lane, Mc, g0);
   }
   // ---- warm start vs smooth acceleration (mjx solver.solve's start) ----
-  // The rows' costs of a start (warm_rows) and the choice between the two (warm_choose) are written once.
+  // The rows' costs of a start (warm_rows) and the choice between the two (warm_choose) are written once for
+  // the latency kernels' halves, and once for both starts together (warm_rows_both, warm_choose_kept).
   // The throughput kernel and physics_kernel run both starts' chains in one fused pass (warm_start). The
   // latency kernels split the pass, so that what needs only qacc_warmstart runs while qacc_smooth is still
   // being solved for: warm_start_a0 (the products of qacc_warmstart: they need M only, not the rows),
@@ -3330,7 +3401,7 @@ struct TPhys {
   }
   // the costs of the lane's rows (its friction row, limit rows and the 4 edges of its contact slot) at
   // qacc_warmstart (W: partial sum cwp, J.x - aref into JA) and at qacc_smooth (S: csp, JV); SL / SR the
-  // feet's motions at qacc_warmstart, SL2 / SR2 at qacc_smooth
+  // feet's motions at qacc_warmstart, SL2 / SR2 at qacc_smooth. The latency kernels' halves, one start each.
   template <bool W, bool S, class V>
   static DK void warm_rows(LP L, int lane, const V& in, const float* SL, const float* SR, const float* SL2,
                            const float* SR2, float& cwp, float& csp) {
@@ -3373,6 +3444,136 @@ struct TPhys {
       }
     }
   }
+  // The rows of both starts in the fused pass (the throughput kernel and physics_kernel), straight-line: every
+  // lane evaluates every kind of row, a lane past a kind's last row on the words of row 0 (the views clamp the
+  // index, so its operands are a real row's), and a select drops its cost. The rows' J.x - aref of both starts
+  // stay in registers (K: .x warm, .y smooth); warm_choose_kept stores the chosen start's. The latency kernels'
+  // halves keep warm_rows and its lane guards: straight-line, every word of a half is loaded at its top, and
+  // step_kernel_lat_x2 (held to 256 registers) spilled 10 registers for its 3 (private segment 416 -> 448 B).
+  struct RowJ { f2v f, l[NLR], c[4]; };
+  template <class V>
+  static DK void warm_rows_both(LP L, int lane, const V& in, const float* SL, const float* SR, const float* SL2,
+                                const float* SR2, float& cwp, float& csp, RowJ& K) {
+    if constexpr (warm_pairs<Md>()) {
+      warm_rows_pair(L, lane, in, SL, SR, SL2, SR2, cwp, csp, K);
+      return;
+    }
+    cwp = csp = 0.0f;
+    {
+      const bool fr = lane < NFRIC;
+      const RowIn x = in.fric();
+      const float jw = x.w - x.ar, js = x.q - x.ar;
+      // (the costs as values of their own: fr ? fric_cost(..) : 0 compiles to a branch over the cost)
+      const float fw = fric_cost(x.D, jw, x.f), fs = fric_cost(x.D, js, x.f);
+      cwp += fr ? fw : 0.0f;
+      csp += fr ? fs : 0.0f;
+      K.f = f2v{jw, js};
+    }
+#pragma unroll
+    for (int m = 0; m < NLR; m++) {
+      const bool ok = TEAM * (m + 1) <= NLIM || lane + TEAM * m < NLIM;
+      const RowIn x = in.lim(m);
+      const float jw = x.sg * x.w - x.ar, js = x.sg * x.q - x.ar;
+      const float lw = side_cost(x.D, jw), ls = side_cost(x.D, js);
+      cwp += ok ? lw : 0.0f;
+      csp += ok ? ls : 0.0f;
+      K.l[m] = f2v{jw, js};
+    }
+    {
+      const bool ok = lane < NCON;
+      const JxIn& jx = in.jx();
+      float vw[4], vs[4];
+      contact_jx(jx, SL, SR, vw);
+      contact_jx(jx, SL2, SR2, vs);
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        const RowIn x = in.con(e);
+        const float jw = vw[e] - x.ar, js = vs[e] - x.ar;
+        const float ew = side_cost(x.D, jw), es = side_cost(x.D, js);
+        cwp += ok ? ew : 0.0f;
+        csp += ok ? es : 0.0f;
+        K.c[e] = f2v{jw, js};
+      }
+    }
+  }
+  // warm_rows_both with the two starts' chains as pairs, .x at qacc_warmstart and .y at qacc_smooth: the
+  // throughput kernel and physics_kernel in the scenes of warm_pairs<Md>() (duck_lspairs.h). Each half is the
+  // operation the scalar form compiles to at that start (profiles/r15_contraction_points.txt): every FMA is
+  // written as one, nothing else may contract (fp contract(off)), compares and selects stay per half. The rows'
+  // words stay scalars and are splat by the packed instruction's operand modifier.
+  static DK f2v sp2(float a) { return f2v{a, a}; }
+  static DK f2v pfma(f2v a, f2v b, f2v c) { return __builtin_elementwise_fma(a, b, c); }
+  static DK f2v side_cost2(float D, f2v j, bool ok) {
+#pragma clang fp contract(off)
+    const f2v q = sp2(0.5f * D) * j * j;
+    return f2v{ok && j.x < 0.0f ? q.x : 0.0f, ok && j.y < 0.0f ? q.y : 0.0f};
+  }
+  template <class V>
+  static DK void warm_rows_pair(LP L, int lane, const V& in, const float* SL, const float* SR, const float* SL2,
+                                const float* SR2, float& cwp, float& csp, RowJ& K) {
+#pragma clang fp contract(off)
+    f2v c;
+    {
+      const bool fr = lane < NFRIC;
+      const RowIn x = in.fric();
+      const f2v j = f2v{x.w, x.q} - sp2(x.ar);
+      // fric_cost's pieces at both starts
+      const float rf = x.f * frcp(x.D), t = 0.5f * rf * x.f;
+      const f2v lo = pfma(j, sp2(-x.f), sp2(-t)), hi = pfma(sp2(x.f), j, sp2(-t)), qd = sp2(0.5f * x.D) * j * j;
+      const float rw = j.x >= rf ? hi.x : qd.x, rs = j.y >= rf ? hi.y : qd.y;
+      const float fw = j.x <= -rf ? lo.x : rw, fs = j.y <= -rf ? lo.y : rs;
+      c = f2v{fr ? fw : 0.0f, fr ? fs : 0.0f};
+      K.f = j;
+    }
+#pragma unroll
+    for (int m = 0; m < NLR; m++) {
+      const int rl = lane + TEAM * m;
+      const bool ok = TEAM * (m + 1) <= NLIM || rl < NLIM;
+      const RowIn x = in.lim(m);
+      const f2v j = pfma(f2v{x.w, x.q}, sp2(x.sg), sp2(-x.ar));
+      c += side_cost2(x.D, j, ok);
+      K.l[m] = j;
+    }
+    {
+      const bool ok = lane < NCON;
+      const JxIn& J = in.jx();
+      // contact_jx at both starts
+      const bool l2 = J.s2 == 1, l1 = J.s1 == 1, n2 = J.s2 != 0, n1 = J.s1 != 0;
+      f2v A[6], B[6];
+#pragma unroll
+      for (int k = 0; k < 6; k++) {
+        A[k] = f2v{l2 ? SL[k] : SR[k], l2 ? SL2[k] : SR2[k]};
+        B[k] = f2v{l1 ? SL[k] : SR[k], l1 ? SL2[k] : SR2[k]};
+      }
+      const f2v r0 = sp2(J.r[0]), r1 = sp2(J.r[1]), r2 = sp2(J.r[2]);
+      // geom 2: Sp + w x r; geom 1: v - (Sp + w x r) as v + ((r x w) - Sp)
+      const f2v t[3] = {A[3] + pfma(r2, A[1], -(r1 * A[2])), pfma(r0, A[2], -(r2 * A[0])) + A[4],
+                        pfma(r1, A[0], -(r0 * A[1])) + A[5]};
+      const f2v u[3] = {pfma(r1, B[2], -(r2 * B[1])) - B[3], pfma(r2, B[0], -(r0 * B[2])) - B[4],
+                        pfma(r0, B[1], -(r1 * B[0])) - B[5]};
+      f2v v[3];
+#pragma unroll
+      for (int a = 0; a < 3; a++) {
+        const f2v va = {n2 ? t[a].x : 0.0f, n2 ? t[a].y : 0.0f}, vb = va + u[a];
+        v[a] = f2v{n1 ? vb.x : va.x, n1 ? vb.y : va.y};
+      }
+      f2v jr[3];
+#pragma unroll
+      for (int q = 0; q < 3; q++)
+        jr[q] = pfma(sp2(J.fr[3 * q + 2]), v[2], pfma(sp2(J.fr[3 * q]), v[0], sp2(J.fr[3 * q + 1]) * v[1]));
+      const f2v mu = sp2(J.mu);
+      const f2v o4[4] = {pfma(mu, jr[1], jr[0]), pfma(-mu, jr[1], jr[0]), pfma(mu, jr[2], jr[0]),
+                         pfma(-mu, jr[2], jr[0])};
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        const RowIn x = in.con(e);
+        K.c[e] = o4[e] - sp2(x.ar);
+        c += side_cost2(x.D, K.c[e], ok);
+      }
+    }
+    cwp = c.x;
+    csp = c.y;
+  }
   // the end of the pass: the Gauss term of qacc_warmstart, 0.5 (M qw - f).(qw - qs), the costs summed over
   // the team, and the cheaper start into QACC / MA / JA. Returns the Gauss cost at that start.
   template <class V>
@@ -3399,6 +3600,48 @@ struct TPhys {
     }
     TSYNC();
     return g0;
+  }
+  // warm_choose of the fused pass: the same sums and the same choice, then the chosen start's words stored from
+  // registers -- QACC, MA and the rows' JA through selects, every lane storing (a lane past the last item into
+  // its sink words). warm_choose copies them between LDS words under the choice's two branches, a round trip per
+  // slice in each, and a wave whose teams choose differently runs both; JV, which only that copy read, is not
+  // written here at all.
+  template <class V>
+  static DK float warm_choose_kept(LP L, int lane, const V& in, float cwp, float csp, const RowJ& K) {
+    float gwp = 0.0f, ma[NC];
+#pragma unroll
+    for (int s = 0; s < NC; s++) {
+      const int c = TEAM * s + lane;
+      const bool ok = TEAM * (s + 1) <= NV || c < NV;
+      const DofIn d = in.dof(s);
+      ma[s] = L[Ly::MA + (ok ? c : 0)];
+      const float g = gwp + 0.5f * (ma[s] - d.fsm) * (d.w - d.q);
+      gwp = ok ? g : gwp;
+    }
+    const float gw = tsum(gwp);
+    const float cw = gw + tsum(cwp), cs = tsum(csp);
+    const bool warm = cw < cs;
+#pragma unroll
+    for (int s = 0; s < NC; s++) {
+      const int c = TEAM * s + lane;
+      const bool ok = TEAM * (s + 1) <= NV || c < NV;
+      const DofIn d = in.dof(s);
+      L[ok ? Ly::QACC + c : TL::SINK + lane] = warm ? d.w : d.q;
+      L[ok ? Ly::MA + c : TL::SINK + TEAM + lane] = warm ? ma[s] : d.fsm;
+    }
+    L[lane < NFRIC ? Ly::JA + lane : TL::SINK + lane] = warm ? K.f.x : K.f.y;
+#pragma unroll
+    for (int m = 0; m < NLR; m++) {
+      const int rl = lane + TEAM * m;
+      const bool ok = TEAM * (m + 1) <= NLIM || rl < NLIM;
+      L[ok ? Ly::JA + R_LIM + rl : TL::SINK + lane] = warm ? K.l[m].x : K.l[m].y;
+    }
+    if (lane < NCON) {
+#pragma unroll
+      for (int e = 0; e < 4; e++) L[Ly::JA + R_CON + 4 * lane + e] = warm ? K.c[e].x : K.c[e].y;
+    }
+    TSYNC();
+    return warm ? gw : 0.0f;
   }
   static DK void warm_start_a0(LP L, int lane, const float (*Mc)[NV], float* SL, float* SR) {
     float sw, ss;
@@ -3438,7 +3681,8 @@ struct TPhys {
     // J and M products of both starts in one pass
     // (M qacc_smooth = qfrc_smooth by definition: no product needed for the smooth start)
     float sw, ss;
-    spatial2(L, lane, Ly::WARM, Ly::QSM, sw, ss);
+    if constexpr (warm_pairs<Md>()) spatial2_pair(L, lane, Ly::WARM, Ly::QSM, sw, ss);
+    else spatial2(L, lane, Ly::WARM, Ly::QSM, sw, ss);
     {
       float xw[NC];
       lane_vec(L, lane, Ly::WARM, xw);
@@ -3450,9 +3694,9 @@ struct TPhys {
     sp_bcast(sw, SL, SR);
     sp_bcast(ss, SL2, SR2);
     STAGE_MARK(ST_WARM_PRODUCTS);
-    warm_rows<true, true>(L, lane, P, SL, SR, SL2, SR2, cwp, csp);
-    bool warm;
-    const float g0 = warm_choose(L, lane, P, cwp, csp, warm);
+    RowJ K;
+    warm_rows_both(L, lane, P, SL, SR, SL2, SR2, cwp, csp, K);
+    const float g0 = warm_choose_kept(L, lane, P, cwp, csp, K);
     STAGE_MARK(ST_WARM_SELECT);
     return g0;
   }
