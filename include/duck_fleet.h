@@ -17,9 +17,11 @@
  * duck_fleet_disturb between duck_fleet_observe and duck_policy_act; and, only when the caller keeps a flight
  * recorder, duck_fleet_record after duck_fleet_actuate; and, only when the caller configures a latency,
  * duck_fleet_actuate_delayed in duck_fleet_actuate's place and, when an IMU delay is among it,
- * duck_fleet_sense_delay right after duck_fleet_observe. A period's order, optional launches in brackets:
+ * duck_fleet_sense_delay right after duck_fleet_observe -- or, when a joint-encoder delay is among it,
+ * duck_fleet_sensor_delay in that place, which delays the IMU and the encoder columns in one launch. A period's
+ * order, optional launches in brackets:
  *
- *   physics, observe, [sense_delay], [disturb], policy or follow, actuate or actuate_delayed, [record]
+ *   physics, observe, [sense_delay or sensor_delay], [disturb], policy or follow, actuate or actuate_delayed, [record]
  *
  * (duck_fleet_follow, in duck_policy_act's place, when the robots follow a recorded log instead of a policy.)
  *
@@ -204,11 +206,13 @@ int duck_fleet_record(const duck_fleet_desc* desc, int N, int depth, int post, c
                       const float* warm, const float* aux, const float* ctl, const float* obs, const float* action,
                       const float* alive, int32_t* head, int32_t* after, float* ring, void* stream);
 
-/* Latency of the deployment loop: the action that reaches the motors and the IMU sample that reaches the policy
- * are each 0 to DUCK_FLEET_MAX_DELAY control periods old (the training env's action delay, joystick.py:361-376,
- * and IMU delay, joystick.py:521-530). A delay is a whole number of periods (20 ms each);
+/* Latency of the deployment loop: the action that reaches the motors, the IMU sample and the joint-encoder
+ * readings that reach the policy are each 0 to DUCK_FLEET_MAX_DELAY control periods old (the training env's
+ * action delay, joystick.py:361-376, and IMU delay, joystick.py:521-530; the encoder delay is the robot's own: its
+ * joint positions and velocities are read back from bus servos over a half-duplex serial line, one after
+ * another, and the training env does not model that). A delay is a whole number of periods (20 ms each);
  * DUCK_FLEET_MAX_DELAY is the depth of the action history the control record already holds. A loop that
- * configures no latency enqueues neither entry.
+ * configures no latency enqueues none of the three entries.
  *
  * lat [N][DUCK_FLEET_LAT_SIZE] row-major int32 = {act_lo, act_hi, sense_lo, sense_hi}, 0 <= lo <= hi <=
  * DUCK_FLEET_MAX_DELAY, validated by the caller; the kernels clamp lo into [0, MAX_DELAY] and hi into
@@ -219,15 +223,16 @@ int duck_fleet_record(const duck_fleet_desc* desc, int N, int depth, int post, c
  *
  * The period's count lives on the device, for duck_fleet_disturb's reason: lat_tick [N] int32, p = lat_tick[e]
  * the periods robot e completed since the latency was configured (0 then, set by the caller). It has one
- * writer, duck_fleet_actuate_delayed, as its last store; duck_fleet_sense_delay, earlier in the period, reads
- * the same p. A negative lat_tick is read as p = 0.
+ * writer, duck_fleet_actuate_delayed, as its last store; duck_fleet_sense_delay and duck_fleet_sensor_delay,
+ * earlier in the period, read the same p. A negative lat_tick is read as p = 0.
  *
  * Random stream, threefry2x32 (20 rounds), apart from the disturbances': key = derive_key(seed, robot_offset + e,
- * DUCK_FLEET_LAT_TAG) (duck_fleet_disturb's key with the other tag; the latency has its own seed). Block 0 of
- * period p is threefry2x32(key, (p, 0)); word 0 draws the action delay, word 1 the sensor delay:
+ * DUCK_FLEET_LAT_TAG) (duck_fleet_disturb's key with the other tag; the latency has its own seed). Block b of
+ * period p is threefry2x32(key, (p, b)). Word 0 of block 0 draws the action delay, word 1 of block 0 the IMU
+ * delay, word 0 of block 1 the encoder delay (word 1 of block 1 is not used):
  *   d = lo + (((word >> 9) * (uint32_t)(hi - lo + 1)) >> 23)
  * in integers: exact, and never above hi. A robot's draws depend on (seed, id, p) only -- not on N, the launch
- * geometry or graph replay.
+ * geometry or graph replay -- and a delay's draws do not depend on whether the other delays are drawn.
  *
  * duck_fleet_sense_delay, after duck_fleet_observe and before duck_fleet_disturb; enqueued only when some robot
  * has sense_hi > 0. line [N][DUCK_FLEET_MAX_DELAY + 1][6] row-major float32 is the robot's delay line of obs
@@ -237,8 +242,26 @@ int duck_fleet_record(const duck_fleet_desc* desc, int N, int depth, int post, c
  * with the words of slot (p - d_eff) % 3; when d_eff == 0 obs is not written. Words are copied as uint32_t:
  * NaN payloads and -0 keep their bits. The noise of duck_fleet_disturb is added after the delay: it is i.i.d.
  * per period, so the sum has the distribution of the training env's noise-then-history order, and the line
- * stays a function of the true sensors. duck_fleet_observe's bookkeeping has run on the true sensors. Only the
- * IMU columns are delayed; joint-encoder latency is not modelled. lat_tick is not written. desc gives nu.
+ * stays a function of the true sensors. duck_fleet_observe's bookkeeping has run on the true sensors. This entry
+ * delays the IMU columns only (the encoder columns: duck_fleet_sensor_delay). lat_tick is not written. desc
+ * gives nu.
+ *
+ * duck_fleet_sensor_delay, in duck_fleet_sense_delay's place (after duck_fleet_observe, before duck_fleet_disturb);
+ * enqueued only when some robot has enc_hi > 0, and then instead of duck_fleet_sense_delay: an encoder delay
+ * adds no launch to a loop that delays the IMU, and one to a loop that does not.
+ * enc [N][DUCK_FLEET_ENC_SIZE] row-major int32 = {enc_lo, enc_hi}, validated and clamped as a pair of lat is.
+ * eline [N][DUCK_FLEET_MAX_DELAY + 1][2 nu] row-major float32 is the robot's delay line of the encoder words:
+ * obs columns 13 .. 13 + 2 nu - 1 as duck_fleet_observe wrote them, qpos[act_qpos[a]] - act_default[a] for a <
+ * nu and then dof_vel_scale * qvel[act_dof[a]] (no noise yet). One delay serves both groups: the position and
+ * the velocity of a joint come from one servo read.
+ *   IMU      duck_fleet_sense_delay's rule, word for word: obs columns 0-5, line, {sense_lo, sense_hi} of lat,
+ *            the draw word 1 of block 0. With enc all zero, obs and line are that entry's bit for bit.
+ *   encoder  for robot e: the 2 nu words go to slot p % 3 of eline (for every robot, whatever its row); then, with d
+ *            the drawn encoder delay and d_eff = min(d, min(p, 2)), when d_eff > 0 the 2 nu obs columns are
+ *            overwritten with the words of slot (p - d_eff) % 3; when d_eff == 0 they are not written.
+ * Words are copied as uint32_t: NaN payloads and -0 keep their bits. No other obs column is written; the noise is
+ * added after the delay and the bookkeeping has run on the true state, as above. lat_tick is not written. desc
+ * gives nu.
  *
  * duck_fleet_actuate_delayed, in duck_fleet_actuate's place. The history shift is duck_fleet_actuate's:
  * last_action etc. hold the policy's undelayed actions (state.info["last_act"] in training). After the shift,
@@ -252,9 +275,13 @@ int duck_fleet_record(const duck_fleet_desc* desc, int N, int depth, int post, c
 #define DUCK_FLEET_MAX_DELAY 2
 #define DUCK_FLEET_LAT_SIZE 4
 #define DUCK_FLEET_LAT_TAG 0x1A7Eu
+#define DUCK_FLEET_ENC_SIZE 2
 
 int duck_fleet_sense_delay(const duck_fleet_desc* desc, int N, uint64_t seed, int64_t robot_offset,
                            const int32_t* lat_tick, const int32_t* lat, float* line, float* obs, void* stream);
+int duck_fleet_sensor_delay(const duck_fleet_desc* desc, int N, uint64_t seed, int64_t robot_offset,
+                            const int32_t* lat_tick, const int32_t* lat, const int32_t* enc,
+                            float* line, float* eline, float* obs, void* stream);
 int duck_fleet_actuate_delayed(const duck_fleet_desc* desc, int N, uint64_t seed, int64_t robot_offset,
                                int32_t* lat_tick, const int32_t* lat, const float* action, float* ctl,
                                float* ctrl, void* stream);
@@ -262,9 +289,9 @@ int duck_fleet_actuate_delayed(const duck_fleet_desc* desc, int N, uint64_t seed
 /* Following a recorded log: the robots are fed the actions a logged robot's policy gave, and every simulated
  * observation is scored against the logged one, per robot and per column (the reference compares the two by eye:
  * its loop and the robot both save what the policy saw, mujoco_infer.py:202, :241, and common/plot_saved_obs.py
- * plots them side by side). In duck_policy_act's place: after duck_fleet_observe, [sense_delay] and [disturb],
- * before duck_fleet_actuate or duck_fleet_actuate_delayed -- a robot's IMU delay and sensor noise are in the
- * observation that is scored, its action delay acts on the fed action. No launch more than the loop with a
+ * plots them side by side). In duck_policy_act's place: after duck_fleet_observe, [sense_delay or
+ * sensor_delay] and [disturb], before duck_fleet_actuate or duck_fleet_actuate_delayed -- a robot's IMU delay,
+ * encoder delay and sensor noise are in the observation that is scored, its action delay acts on the fed action. No launch more than the loop with a
  * policy; a loop without a log does not enqueue it.
  *
  * log [n_log][T][DUCK_FLEET_LOG_SIZE(nu)] row-major float32: row p of a log is the observation the logged

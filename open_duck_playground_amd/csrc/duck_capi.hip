@@ -383,20 +383,22 @@ __global__ __launch_bounds__(FLEET_TPB) void fleet_record_kernel(
   }
 }
 
-// The loop's latency (include/duck_fleet.h: duck_fleet_sense_delay, duck_fleet_actuate_delayed), the same
-// 16-lane group per robot. Every lane of a group loads the robot's counter and its row of the table (broadcast
-// loads) and evaluates the one threefry block itself when the row asks for a draw, so the delay is a value of
-// the whole group with no LDS and no votes. A bad row is clamped: lo into [0, MAX_DELAY], hi into [lo, MAX_DELAY].
-__device__ __forceinline__ int fleet_delay(const int* __restrict__ row, int which, unsigned long long seed,
-                                           long long id, uint32_t p) {
-  int lo = row[2 * which], hi = row[2 * which + 1];
+// The loop's latency (include/duck_fleet.h: duck_fleet_sense_delay, duck_fleet_sensor_delay,
+// duck_fleet_actuate_delayed), the same 16-lane group per robot. Every lane of a group loads the robot's counter
+// and its row of the table (broadcast loads) and evaluates the threefry block itself when the row asks for a
+// draw, so the delay is a value of the whole group with no LDS and no votes. A bad row is clamped: lo into
+// [0, MAX_DELAY], hi into [lo, MAX_DELAY]. `pair` is the {lo, hi} of one delay; its draw is word `word` of block
+// `block` of period p (both constants at every call, so each kernel holds the one block it needs).
+__device__ __forceinline__ int fleet_delay(const int* __restrict__ pair, uint32_t block, int word,
+                                           unsigned long long seed, long long id, uint32_t p) {
+  int lo = pair[0], hi = pair[1];
   lo = lo < 0 ? 0 : (lo > DUCK_FLEET_MAX_DELAY ? DUCK_FLEET_MAX_DELAY : lo);
   hi = hi < lo ? lo : (hi > DUCK_FLEET_MAX_DELAY ? DUCK_FLEET_MAX_DELAY : hi);
   if (hi == lo) return lo;
   uint32_t k0, k1, w0, w1;
   derive_key(seed, id, DUCK_FLEET_LAT_TAG, k0, k1);
-  threefry2x32(k0, k1, p, 0u, w0, w1);
-  return lo + (int)((((which ? w1 : w0) >> 9) * (uint32_t)(hi - lo + 1)) >> 23);
+  threefry2x32(k0, k1, p, block, w0, w1);
+  return lo + (int)((((word ? w1 : w0) >> 9) * (uint32_t)(hi - lo + 1)) >> 23);
 }
 
 // Lanes 0-5 carry the six IMU words: into the line's slot p % 3, then, when the delay reaches back, out of the
@@ -411,7 +413,7 @@ __global__ __launch_bounds__(FLEET_TPB) void fleet_sense_delay_kernel(int nu, in
   if (!fleet_place(n, lane, e) || lane >= 6) return;
   const int p0 = lat_tick[e];
   const uint32_t p = p0 < 0 ? 0u : (uint32_t)p0;
-  const int d = fleet_delay(lat + e * DUCK_FLEET_LAT_SIZE, 1, seed, robot_offset + (long long)e, p);
+  const int d = fleet_delay(lat + e * DUCK_FLEET_LAT_SIZE + 2, 0u, 1, seed, robot_offset + (long long)e, p);
   const uint32_t fill = p < (uint32_t)DUCK_FLEET_MAX_DELAY ? p : (uint32_t)DUCK_FLEET_MAX_DELAY;
   const uint32_t d_eff = (uint32_t)d < fill ? (uint32_t)d : fill;
   constexpr uint32_t SLOTS = DUCK_FLEET_MAX_DELAY + 1;
@@ -419,6 +421,44 @@ __global__ __launch_bounds__(FLEET_TPB) void fleet_sense_delay_kernel(int nu, in
   uint32_t* l = line + e * (SLOTS * 6) + lane;
   l[(p % SLOTS) * 6] = *o;
   if (d_eff > 0) *o = l[((p - d_eff) % SLOTS) * 6];
+}
+
+// fleet_sense_delay_kernel and, by its rule, the joint encoders: lanes 0-5 carry the six IMU words, lane l the
+// encoder words l and l + 16 of obs columns 13 .. 13 + 2 nu - 1, each when < 2 nu (nu <= 16: at most two a lane).
+// The IMU delay is word 1 of block 0, the encoder delay word 0 of block 1; a fixed row evaluates neither.
+// lat_tick is read only.
+__global__ __launch_bounds__(FLEET_TPB) void fleet_sensor_delay_kernel(int nu, int n, unsigned long long seed,
+                                                                       long long robot_offset,
+                                                                       const int* __restrict__ lat_tick,
+                                                                       const int* __restrict__ lat,
+                                                                       const int* __restrict__ enc, uint32_t* line,
+                                                                       uint32_t* eline, uint32_t* obs) {
+  int lane;
+  size_t e;
+  if (!fleet_place(n, lane, e)) return;
+  const int p0 = lat_tick[e];
+  const uint32_t p = p0 < 0 ? 0u : (uint32_t)p0;
+  const long long id = robot_offset + (long long)e;
+  const int ds = fleet_delay(lat + e * DUCK_FLEET_LAT_SIZE + 2, 0u, 1, seed, id, p);
+  const int de = fleet_delay(enc + e * DUCK_FLEET_ENC_SIZE, 1u, 0, seed, id, p);
+  const uint32_t fill = p < (uint32_t)DUCK_FLEET_MAX_DELAY ? p : (uint32_t)DUCK_FLEET_MAX_DELAY;
+  const uint32_t s_eff = (uint32_t)ds < fill ? (uint32_t)ds : fill;
+  const uint32_t e_eff = (uint32_t)de < fill ? (uint32_t)de : fill;
+  constexpr uint32_t SLOTS = DUCK_FLEET_MAX_DELAY + 1;
+  const uint32_t now = p % SLOTS;
+  uint32_t* o = obs + e * DUCK_FLEET_OBS_SIZE(nu);
+  if (lane < 6) {
+    uint32_t* l = line + e * (SLOTS * 6) + lane;
+    l[now * 6] = o[lane];
+    if (s_eff > 0) o[lane] = l[((p - s_eff) % SLOTS) * 6];
+  }
+  const uint32_t W = 2 * (uint32_t)nu;
+  uint32_t* el = eline + e * (SLOTS * W);
+  const uint32_t then = (p - e_eff) % SLOTS;
+  for (uint32_t k = lane; k < W; k += FLEET_TEAM) {
+    el[now * W + k] = o[13 + k];
+    if (e_eff > 0) o[13 + k] = el[then * W + k];
+  }
 }
 
 // fleet_actuate_kernel on history entry d. Every lane has read the counter (one load of the whole wave) before
@@ -434,7 +474,7 @@ __global__ __launch_bounds__(FLEET_TPB) void fleet_actuate_delayed_kernel(const 
   if (!fleet_place(n, a, e)) return;
   const int p0 = lat_tick[e];
   if (a >= D.nu) return;
-  const int d = fleet_delay(lat + e * DUCK_FLEET_LAT_SIZE, 0, seed, robot_offset + (long long)e,
+  const int d = fleet_delay(lat + e * DUCK_FLEET_LAT_SIZE, 0u, 0, seed, robot_offset + (long long)e,
                             p0 < 0 ? 0u : (uint32_t)p0);
   fleet_actuate_body(D, n, e, a, d, action, ctl, ctrl);
   if (a == 0) lat_tick[e] = (int)((uint32_t)p0 + 1u);
@@ -594,6 +634,15 @@ int duck_fleet_sense_delay(const duck_fleet_desc* d, int n, uint64_t seed, int64
   if (int rc = fleet_check("duck_fleet_sense_delay", !lat_tick || !lat || !line || !obs, d, n)) return rc;
   return fleet_launch(fleet_sense_delay_kernel, n, stream, d->nu, n, (unsigned long long)seed, (long long)robot_offset,
                       lat_tick, lat, (uint32_t*)line, (uint32_t*)obs);
+}
+
+int duck_fleet_sensor_delay(const duck_fleet_desc* d, int n, uint64_t seed, int64_t robot_offset, const int32_t* lat_tick,
+                            const int32_t* lat, const int32_t* enc, float* line, float* eline, float* obs, void* stream) {
+  g_err.clear();
+  if (int rc = fleet_check("duck_fleet_sensor_delay", !lat_tick || !lat || !enc || !line || !eline || !obs, d, n))
+    return rc;
+  return fleet_launch(fleet_sensor_delay_kernel, n, stream, d->nu, n, (unsigned long long)seed, (long long)robot_offset,
+                      lat_tick, lat, enc, (uint32_t*)line, (uint32_t*)eline, (uint32_t*)obs);
 }
 
 int duck_fleet_actuate_delayed(const duck_fleet_desc* d, int n, uint64_t seed, int64_t robot_offset, int32_t* lat_tick,

@@ -30,6 +30,7 @@ FLEET_PUSH_SIZE = HEADERS.consts["DUCK_FLEET_PUSH_SIZE"]
 FLEET_MAX_DELAY = HEADERS.consts["DUCK_FLEET_MAX_DELAY"]
 FLEET_LAT_SIZE = HEADERS.consts["DUCK_FLEET_LAT_SIZE"]
 FLEET_LAT_TAG = HEADERS.consts["DUCK_FLEET_LAT_TAG"]
+FLEET_ENC_SIZE = HEADERS.consts["DUCK_FLEET_ENC_SIZE"]
 EXPORTS = list(HEADERS.funcs)
 
 

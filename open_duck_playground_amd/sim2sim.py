@@ -19,8 +19,8 @@ randomised models -- takes thousands of runs. ``python -m open_duck_playground_a
 reference's flags and adds ``--num_robots``, ``--periods``, ``--command_grid``, ``--randomize``, ``--out``, and the
 disturbances the training env has and the reference's deployment loop lacks: ``--push_grid``, ``--push_at``,
 ``--push_every``, ``--push_magnitude``, ``--recovery_window``, ``--noise``, ``--noise_seed``,
-``--resample_commands``; the latency the training env randomises, ``--delay_grid``, ``--delay_jitter``,
-``--delay_seed``; and the flight recorder, ``--record_falls``, ``--record_post``, ``--record_out``,
+``--resample_commands``; the latency the training env randomises and the joint encoders' (``--delay_grid
+NAxNS[xNE]``), ``--delay_jitter``, ``--delay_seed``; and the flight recorder, ``--record_falls``, ``--record_post``, ``--record_out``,
 ``--record_max``: the last periods of every robot that fell, written to an ``.npz`` (the reference keeps what
 its loop saw in ``saved_obs``; the file holds the same observations and the state around them).
 ``--policies P1 P2 ...`` puts several exported policies (the checkpoints of one training run) into one fleet,
@@ -282,14 +282,16 @@ class FleetInfer:
     With none configured the loop is the four launches above, unchanged. ``robot_offset`` is the global id of
     robot 0 in the disturbance stream (a robot's draws depend on the seed, its global id and the period only).
 
-    Latency (off by default; ``set_latency(action, sense, seed)`` or ``latency=(action, sense, seed)``): the
-    action that reaches the motors and the IMU sample that reaches the policy are 0 to 2 control periods old,
-    fixed per robot or drawn per robot and period (the training env's action and IMU delay). With a latency
+    Latency (off by default; ``set_latency(action, sense, seed, encoder)`` or ``latency=(action, sense, seed[,
+    encoder])``): the action that reaches the motors, the IMU sample and the joint-encoder readings that reach the
+    policy are 0 to 2 control periods old, fixed per robot or drawn per robot and period (the training env's action
+    and IMU delay; the encoder delay is the robot's serial servo bus). With a latency
     set, duck_fleet_actuate_delayed takes duck_fleet_actuate's place (no launch more), and with an IMU delay
-    among it duck_fleet_sense_delay runs right after duck_fleet_observe (one launch more): physics -> observe ->
-    [sense_delay] -> [disturb] -> policy -> actuate or actuate_delayed -> [record]. The latency has its own
-    seed and its own period count ``lat_tick`` on the device. With none set (``latent()`` False) the loop
-    enqueues exactly the launches above.
+    among it duck_fleet_sense_delay runs right after duck_fleet_observe (one launch more); with an encoder delay
+    among it duck_fleet_sensor_delay runs in that place and delays both (no launch more than that): physics ->
+    observe -> [sense_delay or sensor_delay] -> [disturb] -> policy -> actuate or actuate_delayed -> [record]. The
+    latency has its own seed and its own period count ``lat_tick`` on the device. With none set (``latent()``
+    False) the loop enqueues exactly the launches above.
 
     The flight recorder (off by default; ``set_recorder(depth, post)`` or ``recorder=(depth, post)``): one more
     launch at the end of the period, duck_fleet_record, keeps every robot's last ``depth`` periods in a ring on
@@ -300,12 +302,12 @@ class FleetInfer:
     loaded from a recorded frame, whose next periods reproduce the robot's bit for bit.
 
     Following a log (off by default; ``set_log(log, ids)`` or ``follow=(log, ids)``): duck_fleet_follow takes
-    duck_policy_act's place (no launch more): physics -> observe -> [sense_delay] -> [disturb] -> policy or follow
-    -> actuate or actuate_delayed -> [record]. The robots are fed the actions and commands of a recorded robot log,
+    duck_policy_act's place (no launch more): physics -> observe -> [sense_delay or sensor_delay] -> [disturb] ->
+    policy or follow -> actuate or actuate_delayed -> [record]. The robots are fed the actions and commands of a recorded robot log,
     and ``scores()`` / ``score_report()`` tell, per robot and observation column, how far the simulated observations
     were from the logged ones: over randomised models and a delay grid, which model the logged robot moves like.
     ``onnx_model_path=None`` is allowed with ``follow``: no policy is loaded. The start state is the loop's own (a log
-    that starts elsewhere is the caller's to load with ``load_state``), and joint-encoder latency is not modelled.
+    that starts elsewhere is the caller's to load with ``load_state``).
     With no log set (``following()`` False) the loop enqueues exactly the launches above.
 
     Several policies (``onnx_model_path`` a list or tuple of K paths, at most DUCK_POLICY_MAX_POLICIES, all of one
@@ -324,7 +326,7 @@ class FleetInfer:
     range (lo != hi) and delay jitter: they are keyed by the robot's global id, so they are independent between
     segments and identically distributed, not common random numbers."""
 
-    # control periods per captured graph (200 launches; 50 more with disturbances, 50 more with an IMU delay, 50 more
+    # control periods per captured graph (200 launches; 50 more with disturbances, 50 more with an IMU or encoder delay, 50 more
     # with a recorder: 400 at the most)
     CHUNK = 50
 
@@ -426,10 +428,11 @@ class FleetInfer:
         self.dis = DuckFleetDisturbance()
         self.sched = self.sched_id = self.push = None
         self.robot_offset = int(robot_offset)
-        # the latency (include/duck_fleet.h duck_fleet_sense_delay, duck_fleet_actuate_delayed): off
-        self.lat = self.lat_tick = self.line = None
+        # the latency (include/duck_fleet.h duck_fleet_sense_delay, duck_fleet_sensor_delay,
+        # duck_fleet_actuate_delayed): off
+        self.lat = self.lat_tick = self.line = self.enc = self.eline = None
         self.lat_seed = self.lat_base = 0
-        self.lat_sense = False
+        self.lat_sense = self.lat_encoder = False
         # following a log (include/duck_fleet.h duck_fleet_follow): off
         self.log = self.log_id = self.log_tick = self.score = None
         self.log_base = 0
@@ -558,6 +561,12 @@ class FleetInfer:
         """duck_fleet_sense_delay on this period's ``obs``: the IMU columns into the delay line and, delayed, back."""
         self._launch("duck_fleet_sense_delay", self.lat_seed, self.robot_offset, self.lat_tick, self.lat, self.line, self.obs)
 
+    def sensor_delay(self):
+        """duck_fleet_sensor_delay on this period's ``obs``: duck_fleet_sense_delay's IMU columns and, by the same
+        rule on their own line, the joint-encoder columns."""
+        self._launch("duck_fleet_sensor_delay", self.lat_seed, self.robot_offset, self.lat_tick, self.lat, self.enc,
+                     self.line, self.eline, self.obs)
+
     def actuate_delayed(self):
         """duck_fleet_actuate_delayed: duck_fleet_actuate on the delayed entry of the history, then lat_tick."""
         self._launch("duck_fleet_actuate_delayed", self.lat_seed, self.robot_offset, self.lat_tick, self.lat, self.action,
@@ -581,10 +590,13 @@ class FleetInfer:
     def _periods(self, k: int, rec: Optional[torch.Tensor] = None, t0: int = 0):
         disturbed, recording = self.disturbed(), self.ring is not None
         sense = self.latent() and self.lat_sense
+        encoder = self.latent() and self.lat_encoder      # the IMU and the encoders in one launch, in sense_delay's place
         for t in range(k):
             self._physics(self.decimation)
             self.observe()
-            if sense:
+            if encoder:
+                self.sensor_delay()
+            elif sense:
                 self.sense_delay()
             if disturbed:
                 self.disturb()
@@ -752,7 +764,7 @@ class FleetInfer:
         [obs_size] defaults to ``default_noise_scales()``. The training env adds the noise to the raw joint
         velocity and scales by dof_vel_scale afterwards; here it is added to the scaled column, with the scale
         multiplied in. duck_fleet_observe's bookkeeping has run on the true sensors. The noise is added after an
-        IMU delay (``set_latency``). ``level=0`` turns the noise off."""
+        IMU or encoder delay (``set_latency``). ``level=0`` turns the noise off."""
         from .native import DuckError
         sc = self.default_noise_scales() if scales is None else np.asarray(scales, dtype=np.float64)
         if sc.shape != (self.obs_size,):
@@ -769,48 +781,34 @@ class FleetInfer:
             self.dis.noise_scale[k] = float(eff[k])
 
     # --- latency (include/duck_fleet.h duck_fleet_sense_delay, duck_fleet_actuate_delayed) ----------------
-    def set_latency(self, action=0, sense=0, seed: int = 0) -> None:
+    def set_latency(self, action=0, sense=0, seed: int = 0, encoder=0) -> None:
         """Latency in whole control periods (20 ms each): ``action`` delays the action that forms the motor targets
         (the training env's action delay, joystick.py:361-376), ``sense`` the gyro and accelerometer columns of the
-        observation (its IMU delay, joystick.py:521-530). Each is a scalar, an [N] list or array of integers, or a
+        observation (its IMU delay, joystick.py:521-530), ``encoder`` the joint-position and joint-velocity columns
+        (the robot's bus servos, read back one after another over a serial line; one delay for both groups; the
+        training env has no such delay). Each is a scalar, an [N] list or array of integers, or a
         tuple ``(lo, hi)`` of such: drawn per robot and period, uniformly over lo..hi with both ends included, from
         the stream of ``seed`` (the latency's own; the training env's randint excludes its upper end: its default
         0..3 is ``(0, 2)`` here). Values lie in [0, 2]. The action history the policy sees stays undelayed, the
-        bookkeeping runs on the true sensors, the noise is added after the delay; the joint encoders are not
-        delayed. ``set_latency(None)``, or all zeros, turns the latency off. A latency starts anew when set: its
-        period count ``lat_tick`` at 0, the delay line empty (``lat_base`` = the periods run since ``restart()``)."""
-        from .native import FLEET_LAT_SIZE, FLEET_MAX_DELAY, DuckError
-        n = self.num_robots
+        bookkeeping runs on the true sensors, the noise is added after the delay. With an encoder delay
+        duck_fleet_sensor_delay takes duck_fleet_sense_delay's place. ``set_latency(None)``, or all zeros, turns the
+        latency off. A latency starts anew when set: its period count ``lat_tick`` at 0, the delay lines empty
+        (``lat_base`` = the periods run since ``restart()``)."""
+        from .native import DuckError
         self.graph = None
-        rows = np.zeros((n, FLEET_LAT_SIZE), dtype=np.int32)
-        if action is not None:
-            for k, (name, v) in enumerate((("action", action), ("sense", sense))):
-                if isinstance(v, tuple) and len(v) != 2:
-                    raise DuckError(f"{name} as a tuple is (lo, hi), got {len(v)} values")
-                for j, (end, w) in enumerate(zip(("lo", "hi"), v if isinstance(v, tuple) else (v, v))):
-                    try:
-                        a = np.asarray(w, dtype=np.float64)
-                    except (TypeError, ValueError):
-                        raise DuckError(f"{name} must be integers, got {w!r}") from None
-                    if a.shape not in ((), (n,)):
-                        raise DuckError(f"{name} must be a scalar or [{n}], got {tuple(a.shape)}")
-                    if not np.isfinite(a).all() or (a != np.floor(a)).any():
-                        raise DuckError(f"{name} must be integers (whole control periods)")
-                    if (a < 0).any() or (a > FLEET_MAX_DELAY).any():
-                        raise DuckError(f"{name} must lie in [0, {FLEET_MAX_DELAY}] control periods")
-                    rows[:, 2 * k + j] = a
-                if (rows[:, 2 * k] > rows[:, 2 * k + 1]).any():
-                    raise DuckError(f"{name} as (lo, hi) needs lo <= hi")
+        rows, enc = latency_rows(self.num_robots, action, sense, encoder)
         if int(seed) != seed:
             raise DuckError(f"the latency seed must be an integer, got {seed!r}")
-        if not rows.any():
-            self.lat = self.lat_tick = self.line = None
-            self.lat_seed, self.lat_sense = 0, False
+        if not rows.any() and not enc.any():
+            self.lat = self.lat_tick = self.line = self.enc = self.eline = None
+            self.lat_seed, self.lat_sense, self.lat_encoder = 0, False, False
             return
-        self._load_latency(rows, seed)
+        self._load_latency(rows, seed, enc)
 
-    def _load_latency(self, rows: np.ndarray, seed: int) -> None:
-        """The latency table ``rows`` [N][4] as it is (all zeros included): new buffers, the count at 0."""
+    def _load_latency(self, rows: np.ndarray, seed: int, enc: Optional[np.ndarray] = None) -> None:
+        """The latency table ``rows`` [N][4] as it is (all zeros included): new buffers, the count at 0. ``enc``
+        [N][2], the encoder table beside it; without one, or with no ``enc_hi`` above 0, the loop is the one without
+        an encoder delay."""
         from .native import FLEET_MAX_DELAY
         n = self.num_robots
         self.graph = None
@@ -819,6 +817,11 @@ class FleetInfer:
         self.line = torch.zeros(n, FLEET_MAX_DELAY + 1, 6, dtype=torch.float32, device=self.device)
         self.lat_seed, self.lat_base = int(seed) & 0xFFFFFFFFFFFFFFFF, self.periods_done
         self.lat_sense = bool((np.asarray(rows)[:, 3] > 0).any())
+        self.enc = self.eline = None
+        self.lat_encoder = enc is not None and bool((np.asarray(enc)[:, 1] > 0).any())
+        if self.lat_encoder:
+            self.enc = torch.as_tensor(np.ascontiguousarray(enc, dtype=np.int32)).to(self.device)
+            self.eline = torch.zeros(n, FLEET_MAX_DELAY + 1, 2 * self.num_dofs, dtype=torch.float32, device=self.device)
 
     # --- following a log (include/duck_fleet.h duck_fleet_follow) ---------------------------------------
     def set_log(self, log, ids=None) -> None:
@@ -828,7 +831,8 @@ class FleetInfer:
         default r mod L). From now on ``act()`` enqueues duck_fleet_follow where it enqueued duck_policy_act: the
         robots are fed the log's actions and commands, and ``score`` [N][obs] sums, per robot and column, the
         squared distance of the simulated observation from the logged one (a NaN log word is a missing sample).
-        A robot's IMU delay and sensor noise are in what is scored, its action delay acts on the fed action.
+        A robot's IMU delay, encoder delay and sensor noise are in what is scored, its action delay acts on the fed
+        action.
         The log starts anew when set: ``log_tick`` and ``score`` zeroed, row 0's command written
         (``log_base`` = the periods run since ``restart()``). The loop's start state is its own: a log that starts
         elsewhere is the caller's to load with ``load_state``. A log rewritten with the same shape keeps the
@@ -937,7 +941,8 @@ class FleetInfer:
         ``recorded(robot)``; negative from the newest): the same model, policy, ``standing`` flag and noise,
         the robot's randomisation record, schedule, push row and latency row, and its global id in the disturbance
         and latency streams. With an IMU delay the delay line is rebuilt from the raw sensors of the frame and of
-        the one before it; a robot whose IMU delay reaches 2 cannot be replayed from the oldest frame it holds.
+        the one before it, with an encoder delay the encoder line from their ``qpos`` and ``qvel``; a robot whose
+        IMU or encoder delay reaches 2 cannot be replayed from the oldest frame it holds.
         Of a following fleet the replay carries the robot's log and ``log_tick`` at the frame's period (its scores
         start at zero).
         The loop is a pure function of what a frame holds, that record and that stream, so running the replay
@@ -981,7 +986,8 @@ class FleetInfer:
             r.log_base = p - after
         if self.latent():
             row = self.lat[robot:robot + 1].cpu().numpy()
-            r._load_latency(row, self.lat_seed)
+            enc = None if self.enc is None else self.enc[robot:robot + 1].cpu().numpy()
+            r._load_latency(row, self.lat_seed, enc)
             after = int(self.lat_tick[robot]) - (self.periods_done - p)   # lat_tick once the frame's period was done
             if after < 0:
                 raise DuckError(f"frame {frame!r} of robot {robot} was written before the latency was set")
@@ -1002,6 +1008,25 @@ class FleetInfer:
                     raise DuckError(f"robot {robot}'s IMU delay reaches 2 periods back and the frame before frame "
                                     f"{frame!r} is not held: replay from a later frame")
                 r.line[0, (q - 1) % 3].copy_(sample(frames[k - 1]))
+            if r.lat_encoder:     # the encoder line by the same rule, from the frames' qpos and qvel
+                nu, d = self.num_dofs, self.desc
+                if self.push is not None and min(d.act_dof[:nu]) < 2:
+                    raise DuckError("an actuated joint's velocity is qvel[0] or qvel[1], where a frame holds the next "
+                                    "period's push: the encoder line cannot be rebuilt from the frames")
+                oq, ov = self.frame_fields["qpos"][0], self.frame_fields["qvel"][0]
+
+                def joints(fr):   # obs columns 13 .. 13 + 2 nu - 1 as duck_fleet_observe wrote them
+                    fr = np.asarray(fr, dtype=np.float32)
+                    pos = fr[oq + np.array(d.act_qpos[:nu])] - np.array(d.act_default[:nu], dtype=np.float32)
+                    vel = np.float32(d.dof_vel_scale) * fr[ov + np.array(d.act_dof[:nu])]
+                    return torch.tensor(np.concatenate([pos, vel]).astype(np.float32), device=self.device)
+                if q >= 0:
+                    r.eline[0, q % 3].copy_(joints(frames[k]))
+                if q >= 1 and int(enc[0, 1]) == 2:
+                    if k == 0:
+                        raise DuckError(f"robot {robot}'s encoder delay reaches 2 periods back and the frame before "
+                                        f"frame {frame!r} is not held: replay from a later frame")
+                    r.eline[0, (q - 1) % 3].copy_(joints(frames[k - 1]))
         r.periods_done = p
         return r
 
@@ -1189,16 +1214,48 @@ def disturbance_plan(args, cells: np.ndarray):
 PERIOD_MS = 20.0   # one control period: sim_dt * decimation = 0.002 s * 10
 
 
-def delay_grid(spec: str) -> np.ndarray:
+def latency_rows(n: int, action=0, sense=0, encoder=0) -> Tuple[np.ndarray, np.ndarray]:
+    """``FleetInfer.set_latency``'s arguments for ``n`` robots as the device's tables: (``lat`` [n][4] int32 =
+    {act_lo, act_hi, sense_lo, sense_hi}, ``enc`` [n][2] int32 = {enc_lo, enc_hi}). Each argument is a scalar, [n],
+    or a tuple (lo, hi) of such, whole periods in [0, DUCK_FLEET_MAX_DELAY]; DuckError otherwise. ``action=None``
+    is all zeros."""
+    from .native import FLEET_ENC_SIZE, FLEET_LAT_SIZE, FLEET_MAX_DELAY, DuckError
+    both = np.zeros((n, FLEET_LAT_SIZE + FLEET_ENC_SIZE), dtype=np.int32)
+    if action is not None:
+        for k, (name, v) in enumerate((("action", action), ("sense", sense), ("encoder", encoder))):
+            if isinstance(v, tuple) and len(v) != 2:
+                raise DuckError(f"{name} as a tuple is (lo, hi), got {len(v)} values")
+            for j, (end, w) in enumerate(zip(("lo", "hi"), v if isinstance(v, tuple) else (v, v))):
+                try:
+                    a = np.asarray(w, dtype=np.float64)
+                except (TypeError, ValueError):
+                    raise DuckError(f"{name} must be integers, got {w!r}") from None
+                if a.shape not in ((), (n,)):
+                    raise DuckError(f"{name} must be a scalar or [{n}], got {tuple(a.shape)}")
+                if not np.isfinite(a).all() or (a != np.floor(a)).any():
+                    raise DuckError(f"{name} must be integers (whole control periods)")
+                if (a < 0).any() or (a > FLEET_MAX_DELAY).any():
+                    raise DuckError(f"{name} must lie in [0, {FLEET_MAX_DELAY}] control periods")
+                both[:, 2 * k + j] = a
+            if (both[:, 2 * k] > both[:, 2 * k + 1]).any():
+                raise DuckError(f"{name} as (lo, hi) needs lo <= hi")
+    return np.ascontiguousarray(both[:, :FLEET_LAT_SIZE]), np.ascontiguousarray(both[:, FLEET_LAT_SIZE:])
+
+
+def delay_grid(spec: str, encoder: bool = False) -> np.ndarray:
     """``NAxNS`` -> the [NA * NS][2] (action delay, sense delay) cells in control periods: a in range(NA), s in
-    range(NS), 1 <= NA, NS <= DUCK_FLEET_MAX_DELAY + 1."""
+    range(NS), 1 <= NA, NS <= DUCK_FLEET_MAX_DELAY + 1. With ``encoder=True`` (the command line's way) a third
+    field is allowed too: ``NAxNSxNE`` -> the [NA * NS * NE][3] (action, sense, encoder delay) cells, the encoder
+    delay e in range(NE) fastest. Without it a spec of three fields is refused, as it always was: a caller that
+    unpacks two columns is never handed three."""
     from .native import FLEET_MAX_DELAY
     try:
-        na, ns = (int(v) for v in spec.lower().split("x"))
-        assert 1 <= min(na, ns) and max(na, ns) <= FLEET_MAX_DELAY + 1
+        sizes = [int(v) for v in spec.lower().split("x")]
+        assert len(sizes) in ((2, 3) if encoder else (2,)) and 1 <= min(sizes) and max(sizes) <= FLEET_MAX_DELAY + 1
     except Exception:
-        raise ValueError(f"--delay_grid wants NAxNS with 1 <= NA, NS <= {FLEET_MAX_DELAY + 1}, got {spec!r}") from None
-    return np.array([(a, s) for a in range(na) for s in range(ns)], dtype=np.int32)
+        form = "NAxNS or NAxNSxNE with 1 <= NA, NS, NE" if encoder else "NAxNS with 1 <= NA, NS"
+        raise ValueError(f"--delay_grid wants {form} <= {FLEET_MAX_DELAY + 1}, got {spec!r}") from None
+    return np.array(list(np.ndindex(*sizes)), dtype=np.int32)
 
 
 def robot_delay_cells(num_robots: int, n_command: int, n_push: int, n_delay: int) -> np.ndarray:
@@ -1210,18 +1267,25 @@ def robot_delay_cells(num_robots: int, n_command: int, n_push: int, n_delay: int
 def latency_plan(args, n_command: int, n_push: int = 1):
     """The command line's latency flags, or None without ``--delay_grid``: {"cells" [D][2], "cell" [N],
     "latency": ``set_latency``'s arguments, "echo": the settings for the report}. With ``--delay_jitter`` a robot
-    draws per period from [0, its cell's value] instead of holding it."""
+    draws per period from [0, its cell's value] instead of holding it. A grid ``NAxNSxNE`` has cells [D][3] and
+    the encoder delay as the fourth of ``set_latency``'s arguments."""
     if args.delay_grid is None:
         if args.delay_jitter:
             raise ValueError("--delay_jitter needs --delay_grid NAxNS")
         return None
-    cells = delay_grid(args.delay_grid)
+    cells = delay_grid(args.delay_grid, encoder=True)
     cell = robot_delay_cells(args.num_robots, n_command, n_push, len(cells))
-    a, s = cells[cell, 0], cells[cell, 1]
-    zero = np.zeros_like(a)
-    latency = ((zero, a), (zero, s), args.delay_seed) if args.delay_jitter else (a, s, args.delay_seed)
+    latency = cell_latency(cells, cell, args.delay_jitter, args.delay_seed)
     echo = {"delay_grid": args.delay_grid, "delay_jitter": bool(args.delay_jitter), "delay_seed": args.delay_seed}
     return {"cells": cells, "cell": cell, "latency": latency, "echo": echo}
+
+
+def cell_latency(cells: np.ndarray, cell: np.ndarray, jitter: bool, seed: int) -> tuple:
+    """``set_latency``'s arguments (action, sense, seed[, encoder]) for robots in the delay cells ``cell`` [N] of
+    ``cells`` [D][2 or 3]: each robot's cell values held, or with ``jitter`` drawn from [0, the value]."""
+    zero = np.zeros_like(cells[cell, 0])
+    cols =[((zero, cells[cell, k]) if jitter else cells[cell, k]) for k in range(cells.shape[1])]
+    return (cols[0], cols[1], seed, *cols[2:])
 
 
 def latency_report(rep: Dict[str, np.ndarray], acc: np.ndarray, delay_cell: np.ndarray, cells: np.ndarray,
@@ -1237,17 +1301,21 @@ def latency_report(rep: Dict[str, np.ndarray], acc: np.ndarray, delay_cell: np.n
         tot = a.sum(0) if len(a) else np.zeros(6)
         rms = (lambda v: float(np.sqrt(v / tot[0]))) if tot[0] > 0 else (lambda v: None)
         da, ds = int(cells[c][0]), int(cells[c][1])
-        out.append({"cell": c, "action_delay": da, "sense_delay": ds, "action_delay_ms": da * PERIOD_MS,
-                    "sense_delay_ms": ds * PERIOD_MS, "jitter": bool(jitter), "count": int(len(a)),
-                    "survival_rate": float(np.mean(~np.asarray(rep["fell"], dtype=bool)[m])) if len(a) else None,
-                    "mean_periods": float(a[:, 0].mean()) if len(a) else None, "periods": int(n_periods),
-                    "rms_lin_err": rms(tot[4]), "rms_yaw_err": rms(tot[5])})
+        row = {"cell": c, "action_delay": da, "sense_delay": ds, "action_delay_ms": da * PERIOD_MS,
+               "sense_delay_ms": ds * PERIOD_MS, "jitter": bool(jitter), "count": int(len(a)),
+               "survival_rate": float(np.mean(~np.asarray(rep["fell"], dtype=bool)[m])) if len(a) else None,
+               "mean_periods": float(a[:, 0].mean()) if len(a) else None, "periods": int(n_periods),
+               "rms_lin_err": rms(tot[4]), "rms_yaw_err": rms(tot[5])}
+        if len(cells[c]) > 2:     # a grid with the encoder axis
+            row["encoder_delay"], row["encoder_delay_ms"] = int(cells[c][2]), int(cells[c][2]) * PERIOD_MS
+        out.append(row)
     return out
 
 
 def add_latency_arguments(p) -> None:
-    p.add_argument("--delay_grid", type=str, default=None, metavar="NAxNS",
-                   help="action delays 0..NA-1 x IMU delays 0..NS-1 in control periods of 20 ms (NA, NS <= 3)")
+    p.add_argument("--delay_grid", type=str, default=None, metavar="NAxNS[xNE]",
+                   help="action delays 0..NA-1 x IMU delays 0..NS-1 [x joint-encoder delays 0..NE-1] in control "
+                        "periods of 20 ms (NA, NS, NE <= 3)")
     p.add_argument("--delay_jitter", action="store_true", default=False,
                    help="draw each robot's delays per period from [0, its cell's value] instead of holding them")
     p.add_argument("--delay_seed", type=int, default=0, metavar="SEED")
@@ -1548,6 +1616,8 @@ def follow_round(fleet: "FleetInfer", rep: Dict[str, np.ndarray], survived, elit
         if delays is not None:
             c = int(delays["cell"][e])
             row["delay_cell"] = {"cell": c, "action_delay": int(delays["cells"][c][0]), "sense_delay": int(delays["cells"][c][1])}
+            if len(delays["cells"][c]) > 2:
+                row["delay_cell"]["encoder_delay"] = int(delays["cells"][c][2])
         if dr is not None:
             ends = [layout[k] for k in names[1:]] + [layout["nfloat"]]
             row["randomization"] = {k: [float(v) for v in dr[layout[k]:end, e]] for k, end in zip(names, ends)}
@@ -1799,9 +1869,7 @@ def main(argv=None) -> int:
                 if delays is not None:     # an elite robot keeps its delay cell, a new one draws an elite's
                     cell = delays["cell"][order[:elite]]
                     cell = delays["cell"] = np.concatenate([cell, rng.choice(cell, n - elite)])
-                    a, s = delays["cells"][cell, 0], delays["cells"][cell, 1]
-                    zero = np.zeros_like(a)
-                    fleet.set_latency(*(((zero, a), (zero, s)) if args.delay_jitter else (a, s)), args.delay_seed)
+                    fleet.set_latency(*cell_latency(delays["cells"], cell, args.delay_jitter, args.delay_seed))
                 fleet.restart()
                 fleet.run(args.periods)
             srep = fleet.score_report(weights)
