@@ -18,10 +18,15 @@
  * recorder, duck_fleet_record after duck_fleet_actuate; and, only when the caller configures a latency,
  * duck_fleet_actuate_delayed in duck_fleet_actuate's place and, when an IMU delay is among it,
  * duck_fleet_sense_delay right after duck_fleet_observe -- or, when a joint-encoder delay is among it,
- * duck_fleet_sensor_delay in that place, which delays the IMU and the encoder columns in one launch. A period's
+ * duck_fleet_sensor_delay in that place, which delays the IMU and the encoder columns in one launch; and, only
+ * when the caller asks how the robots walk and load their servos, duck_fleet_gait after the actuation. A period's
  * order, optional launches in brackets:
  *
  *   physics, observe, [sense_delay or sensor_delay], [disturb], policy or follow, actuate or actuate_delayed, [record]
+ *
+ * and, with the gait record kept, duck_fleet_gait between the actuation and the recorder:
+ *
+ *   ..., policy or follow, actuate or actuate_delayed, [gait], [record]
  *
  * (duck_fleet_follow, in duck_policy_act's place, when the robots follow a recorded log instead of a policy.)
  *
@@ -317,6 +322,79 @@ int duck_fleet_actuate_delayed(const duck_fleet_desc* desc, int N, uint64_t seed
 
 int duck_fleet_follow(const duck_fleet_desc* desc, int N, int n_log, int T, const float* log, const int32_t* log_id,
                       int32_t* log_tick, const float* obs, float* score, float* ctl, float* action, void* stream);
+
+/* Gait and servo load: how a robot that stays up does it -- how hard the servos push and how close to their force
+ * and speed limits, how much the actions chatter, how the feet step, slip and clear the ground (the training env
+ * prices some of these as costs, joystick.py `torques` and `action_rate`; the deployment loop has none of them).
+ * One more launch, after duck_fleet_actuate or duck_fleet_actuate_delayed, so that history entry 0 is this period's
+ * action and entry 1 the one before, and before duck_fleet_record, which stays last; a loop that does not ask for
+ * it does not enqueue it. It reads this period's aux, qvel, ctl and alive and writes gait only.
+ *
+ * What is sampled: the period's last substep, 50 Hz. Peaks are peaks of those samples, and work is a 50 Hz
+ * sampling of a 500 Hz signal.
+ *
+ * gait [N][DUCK_FLEET_GAIT_SIZE(nu)] row-major float32, zeroed by the caller; with B = 7 nu:
+ *   [0, nu)        force_sq      sum of f^2
+ *   [nu, 2nu)      force_max     max |f|
+ *   [2nu, 3nu)     force_sat     periods with |f| >= force_sat[a]
+ *   [3nu, 4nu)     speed_max     max |w|
+ *   [4nu, 5nu)     speed_sat     periods with |w| >= speed_sat
+ *   [5nu, 6nu)     work          sum of |f * w|
+ *   [6nu, 7nu)     action_rate   sum of (last_action - last_last_action)^2
+ *   B              periods       periods accumulated
+ *   B + 1          double_support   periods with both feet in contact
+ *   B + 2          flight           periods with neither foot in contact
+ *   B + 3 + 6 f    foot f = 0 (left), 1 (right): contact, touchdowns, slip, apex_sum, prev (state), apex (state)
+ * Counts are float adds of 1, exact below 2^24.
+ *
+ * For robot e, only while alive[e] != 0 (acc's rule: a dead robot gets no word written, the state words included;
+ * duck_fleet_observe has cleared alive in the period of the fall, so that period is not accumulated and periods
+ * equals acc[e][0] when both were zeroed together). With first = (gait[e][B] == 0), read before any store of the
+ * call:
+ *   actuator a < nu   f = aux[4 nv + a][e] (actuator_force, write_aux's order), w = qvel[act_dof[a]][e], af = |f|,
+ *            aw = |w|: force_sq += f * f; force_max = af > force_max ? af : force_max (a NaN never enters a
+ *            maximum); force_sat += 1 when af >= force_sat[a] (a NaN is not counted); the same two for aw against
+ *            speed_sat; work += |f * w|; d = last_action[a] - last_last_action[a], action_rate += d * d.
+ *   foot f   c = duck_fleet_observe's contact (any of the four con_dist slots at con_off + foot_con[f] is < 0);
+ *            vx, vy = sensordata words foot_linvel[f] + 0, 1; z = word foot_pos[f] + 2.
+ *            When c: contact += 1, slip += (vx * vx) + (vy * vy) (two products, their sum, the add).
+ *            touchdown = !first && prev == 0 && c; liftoff = !first && prev != 0 && !c.
+ *            When !c: apex = (first || liftoff) ? z : (z > apex ? z : apex).
+ *            When touchdown: touchdowns += 1, apex_sum += apex - z (the subtraction, then the add): the height of
+ *            the swing's highest sample over the landing sample.
+ *            Last, prev = c ? 1 : 0.
+ *   body     double_support += 1 when both feet are in contact, flight += 1 when neither is; periods += 1, the
+ *            robot's last store.
+ * Every value written is one fp32 operation on loaded words, each rounded on its own.
+ *
+ * DUCK_EINVAL on duck_fleet_observe's descriptor checks, 4 nv + nu > naux, or one of the four foot sensor
+ * addresses outside the sensordata rows (adr < 0 or sens_off + adr + 3 > con_off). N == 0 launches nothing. */
+typedef struct duck_fleet_gait_desc duck_fleet_gait_desc; /* the second host descriptor: its fields are stated in */
+#include "duck_fleet_gait.h"                              /* duck_fleet_gait.h, which this header brings along */
+
+/* The first word of each field (each macro in its own arguments only, as the sizes are): */
+#define DUCK_FLEET_GAIT_FORCE_SQ(nu) (0 * (nu))
+#define DUCK_FLEET_GAIT_FORCE_MAX(nu) (1 * (nu))
+#define DUCK_FLEET_GAIT_FORCE_SAT(nu) (2 * (nu))
+#define DUCK_FLEET_GAIT_SPEED_MAX(nu) (3 * (nu))
+#define DUCK_FLEET_GAIT_SPEED_SAT(nu) (4 * (nu))
+#define DUCK_FLEET_GAIT_WORK(nu) (5 * (nu))
+#define DUCK_FLEET_GAIT_ACTION_RATE(nu) (6 * (nu))
+#define DUCK_FLEET_GAIT_PERIODS(nu) (7 * (nu))
+#define DUCK_FLEET_GAIT_DOUBLE_SUPPORT(nu) (7 * (nu) + 1)
+#define DUCK_FLEET_GAIT_FLIGHT(nu) (7 * (nu) + 2)
+#define DUCK_FLEET_GAIT_FOOT(nu, f) (7 * (nu) + 3 + 6 * (f)) /* foot f = 0, 1; then, inside a foot's six words: */
+#define DUCK_FLEET_GAIT_FOOT_CONTACT 0
+#define DUCK_FLEET_GAIT_FOOT_TOUCHDOWNS 1
+#define DUCK_FLEET_GAIT_FOOT_SLIP 2
+#define DUCK_FLEET_GAIT_FOOT_APEX_SUM 3
+#define DUCK_FLEET_GAIT_FOOT_PREV 4
+#define DUCK_FLEET_GAIT_FOOT_APEX 5
+#define DUCK_FLEET_GAIT_FOOT_SIZE 6
+#define DUCK_FLEET_GAIT_SIZE(nu) (7 * (nu) + 15)
+
+int duck_fleet_gait(const duck_fleet_desc* desc, const duck_fleet_gait_desc* gait_desc, int N, const float* qvel,
+                    const float* aux, const float* ctl, const float* alive, float* gait, void* stream);
 
 #ifdef __cplusplus
 }

@@ -27,6 +27,9 @@ INCLUDE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "includ
 HEADERS = cdecl.Header(*(os.path.join(INCLUDE, f) for f in ("duck_model.h", "duck_env.h", "duck.h", "duck_ppo.h",
                                                             "duck_fleet.h")),
                        address_structs=("duck_mlp_problem", "duck_gather_field"))
+# duck_fleet_gait's descriptor has a header of its own (duck_fleet.h declares the type and includes it), read on
+# top of the others: a duck_fleet_gait_desc* parameter of HEADERS' prototypes is an address, which takes byref
+FLEET_GAIT_HEADERS = cdecl.Header(os.path.join(INCLUDE, "duck_fleet_gait.h"), base=HEADERS)
 
 # words (uint64) of duck_debug_stage_cycles' buffer
 STAGE_CYCLES_WORDS = HEADERS.consts["DUCK_STAGE_CYCLES_WORDS"]

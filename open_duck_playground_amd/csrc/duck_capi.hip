@@ -520,6 +520,83 @@ __global__ __launch_bounds__(FLEET_TPB) void fleet_follow_kernel(int nu, int n, 
   if (lane == 0) log_tick[e] = inside ? p + 1 : T;
 }
 
+// Gait and servo load (include/duck_fleet.h: duck_fleet_gait), the same 16-lane group per robot, after the
+// actuation. Lane a < nu carries actuator a through the seven per-actuator blocks of the record, so the group reads
+// and writes runs of nu consecutive words of the robot's row, and reads the actuator_force and qvel rows next to
+// the neighbouring groups'. Lanes 0 and 1 also carry the left and the right foot (six consecutive words each;
+// both look at both feet's contact slots, eight loads of a wave either way), lane 0 the three whole-body words.
+// Every lane has read the periods word, which tells `first` (one load of the whole wave), before lane 0's store
+// of it, which depends on that load, can issue; it is the robot's last store. A dead robot's group leaves before
+// any store. No LDS, no votes: lanes past the last robot leave.
+__global__ __launch_bounds__(FLEET_TPB) void fleet_gait_kernel(const duck_fleet_desc D, const duck_fleet_gait_desc S,
+                                                               int n, const float* __restrict__ qvel,
+                                                               const float* __restrict__ aux,
+                                                               const float* __restrict__ ctl,
+                                                               const float* __restrict__ alive, float* gait) {
+#pragma clang fp contract(off)
+  int lane;
+  size_t e;
+  if (!fleet_place(n, lane, e)) return;
+  if (alive[e] == 0.f) return;
+  const size_t N = n;
+  const int nu = D.nu, B = DUCK_FLEET_GAIT_PERIODS(nu);
+  float* g = gait + e * DUCK_FLEET_GAIT_SIZE(nu);
+  const float periods = g[B];
+  const bool first = periods == 0.f;
+  if (lane < nu) {
+    const int a = lane;
+    const float* c = ctl + e * DUCK_FLEET_CTL_SIZE(nu);
+    const float f = aux[(size_t)(4 * D.nv + a) * N + e], w = qvel[(size_t)D.act_dof[a] * N + e];
+    const float af = __builtin_fabsf(f), aw = __builtin_fabsf(w);
+    const float ff = f * f, fw = f * w;
+    const float d = c[DUCK_FLEET_CTL_ACTION(nu, 0) + a] - c[DUCK_FLEET_CTL_ACTION(nu, 1) + a];
+    const float dd = d * d;
+    float* r = g + a;
+    const float fmax = r[DUCK_FLEET_GAIT_FORCE_MAX(nu)], wmax = r[DUCK_FLEET_GAIT_SPEED_MAX(nu)];
+    r[DUCK_FLEET_GAIT_FORCE_SQ(nu)] = r[DUCK_FLEET_GAIT_FORCE_SQ(nu)] + ff;
+    r[DUCK_FLEET_GAIT_FORCE_MAX(nu)] = af > fmax ? af : fmax;  // a NaN never enters
+    if (af >= S.force_sat[a]) r[DUCK_FLEET_GAIT_FORCE_SAT(nu)] = r[DUCK_FLEET_GAIT_FORCE_SAT(nu)] + 1.f;
+    r[DUCK_FLEET_GAIT_SPEED_MAX(nu)] = aw > wmax ? aw : wmax;
+    if (aw >= S.speed_sat) r[DUCK_FLEET_GAIT_SPEED_SAT(nu)] = r[DUCK_FLEET_GAIT_SPEED_SAT(nu)] + 1.f;
+    r[DUCK_FLEET_GAIT_WORK(nu)] = r[DUCK_FLEET_GAIT_WORK(nu)] + __builtin_fabsf(fw);
+    r[DUCK_FLEET_GAIT_ACTION_RATE(nu)] = r[DUCK_FLEET_GAIT_ACTION_RATE(nu)] + dd;
+  }
+  if (lane < 2) {
+    // duck_fleet_observe's contact of both feet
+    const float* l = aux + (size_t)(D.con_off + D.foot_con[0]) * N + e;
+    const float* r4 = aux + (size_t)(D.con_off + D.foot_con[1]) * N + e;
+    const bool c0 = (l[0] < 0.f) | (l[N] < 0.f) | (l[2 * N] < 0.f) | (l[3 * N] < 0.f);
+    const bool c1 = (r4[0] < 0.f) | (r4[N] < 0.f) | (r4[2 * N] < 0.f) | (r4[3 * N] < 0.f);
+    const bool cf = lane ? c1 : c0;
+    const float* sens = aux + (size_t)D.sens_off * N + e;
+    const int lin = lane ? S.foot_linvel[1] : S.foot_linvel[0], pos = lane ? S.foot_pos[1] : S.foot_pos[0];
+    float* r = g + DUCK_FLEET_GAIT_FOOT(nu, lane);
+    const float prev = r[DUCK_FLEET_GAIT_FOOT_PREV], apex = r[DUCK_FLEET_GAIT_FOOT_APEX];
+    const float z = sens[(size_t)(pos + 2) * N];
+    const bool touchdown = !first && prev == 0.f && cf, liftoff = !first && prev != 0.f && !cf;
+    if (cf) {
+      const float vx = sens[(size_t)lin * N], vy = sens[(size_t)(lin + 1) * N];
+      const float xx = vx * vx, yy = vy * vy;
+      const float s = xx + yy;
+      r[DUCK_FLEET_GAIT_FOOT_CONTACT] = r[DUCK_FLEET_GAIT_FOOT_CONTACT] + 1.f;
+      r[DUCK_FLEET_GAIT_FOOT_SLIP] = r[DUCK_FLEET_GAIT_FOOT_SLIP] + s;
+    } else {
+      r[DUCK_FLEET_GAIT_FOOT_APEX] = (first || liftoff) ? z : (z > apex ? z : apex);
+    }
+    if (touchdown) {
+      const float h = apex - z;
+      r[DUCK_FLEET_GAIT_FOOT_TOUCHDOWNS] = r[DUCK_FLEET_GAIT_FOOT_TOUCHDOWNS] + 1.f;
+      r[DUCK_FLEET_GAIT_FOOT_APEX_SUM] = r[DUCK_FLEET_GAIT_FOOT_APEX_SUM] + h;
+    }
+    r[DUCK_FLEET_GAIT_FOOT_PREV] = cf ? 1.f : 0.f;
+    if (lane == 0) {
+      if (c0 && c1) g[DUCK_FLEET_GAIT_DOUBLE_SUPPORT(nu)] = g[DUCK_FLEET_GAIT_DOUBLE_SUPPORT(nu)] + 1.f;
+      if (!c0 && !c1) g[DUCK_FLEET_GAIT_FLIGHT(nu)] = g[DUCK_FLEET_GAIT_FLIGHT(nu)] + 1.f;
+      g[B] = periods + 1.f;
+    }
+  }
+}
+
 static const char* fleet_desc_error(const duck_fleet_desc* d) {
   if (d->nq < 1 || d->nv < 1 || d->nu < 1 || d->nu > DUCK_FLEET_MAX_NU) return "nq, nv >= 1 and 1 <= nu <= 16";
   for (int a = 0; a < d->nu; a++)
@@ -661,6 +738,23 @@ int duck_fleet_follow(const duck_fleet_desc* d, int n, int n_log, int T, const f
     return rc;
   return fleet_launch(fleet_follow_kernel, n, stream, d->nu, n, n_log, T, (const uint32_t*)log, log_id, log_tick, obs,
                       score, (uint32_t*)ctl, (uint32_t*)action);
+}
+
+int duck_fleet_gait(const duck_fleet_desc* d, const duck_fleet_gait_desc* s, int n, const float* qvel, const float* aux,
+                    const float* ctl, const float* alive, float* gait, void* stream) {
+  g_err.clear();
+  if (int rc = fleet_check("duck_fleet_gait", !s || !qvel || !aux || !ctl || !alive || !gait, d, n)) return rc;
+  if (!fleet_sensors_inside(d))
+    return duck_fail(DUCK_EINVAL, "duck_fleet_gait: sensor address outside the aux record");
+  for (int f : d->foot_con)
+    if (f < 0 || d->con_off < 0 || (long long)d->con_off + f + 4 > d->naux)
+      return duck_fail(DUCK_EINVAL, "duck_fleet_gait: contact slot outside the aux record");
+  if (4LL * d->nv + d->nu > d->naux)
+    return duck_fail(DUCK_EINVAL, "duck_fleet_gait: actuator_force rows (4 nv + nu) outside the aux record");
+  for (int adr : {s->foot_linvel[0], s->foot_linvel[1], s->foot_pos[0], s->foot_pos[1]})
+    if (adr < 0 || (long long)d->sens_off + adr + 3 > d->con_off)
+      return duck_fail(DUCK_EINVAL, "duck_fleet_gait: foot sensor address outside the sensordata rows");
+  return fleet_launch(fleet_gait_kernel, n, stream, *d, *s, n, qvel, aux, ctl, alive, gait);
 }
 
 uint64_t duck_model_fingerprint(const duck_model_desc* m) {

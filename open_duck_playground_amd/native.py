@@ -10,7 +10,7 @@ import ctypes as C
 import os
 import subprocess
 
-from .cabi import HEADERS
+from .cabi import FLEET_GAIT_HEADERS, HEADERS
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DUCK_LIB") or os.path.join(HERE, "libduck.so")
@@ -24,6 +24,7 @@ DuckLayout = HEADERS.structs["duck_layout"]
 DuckMlpProblem = HEADERS.structs["duck_mlp_problem"]
 DuckGatherField = HEADERS.structs["duck_gather_field"]
 DuckFleetDesc = HEADERS.structs["duck_fleet_desc"]
+DuckFleetGaitDesc = FLEET_GAIT_HEADERS.structs["duck_fleet_gait_desc"]   # (include/duck_fleet_gait.h)
 DuckFleetDisturbance = HEADERS.structs["duck_fleet_disturbance"]
 FLEET_MAX_NU = HEADERS.consts["DUCK_FLEET_MAX_NU"]
 FLEET_PUSH_SIZE = HEADERS.consts["DUCK_FLEET_PUSH_SIZE"]

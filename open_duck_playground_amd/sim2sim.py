@@ -25,6 +25,8 @@ NAxNS[xNE]``), ``--delay_jitter``, ``--delay_seed``; and the flight recorder, ``
 its loop saw in ``saved_obs``; the file holds the same observations and the state around them).
 ``--policies P1 P2 ...`` puts several exported policies (the checkpoints of one training run) into one fleet,
 ``--num_robots`` / K robots each on the same models, commands, push cells and delays, and ranks them.
+``--gait`` (``--gait_force_frac``, ``--gait_speed_frac``) keeps a gait and servo-load record per robot on the device
+and adds its summary to the report: for the fleet, per command cell and per policy.
 """
 
 from __future__ import annotations
@@ -258,6 +260,48 @@ def fleet_desc(m, naux: int, nb_steps_in_period: int, standing: bool, speed_limi
     return d
 
 
+MAX_MOTOR_VELOCITY = 5.24     # rad/s, mujoco_infer.py:58
+GAIT_ACTUATOR_FIELDS = ("force_sq", "force_max", "force_sat", "speed_max", "speed_sat", "work", "action_rate")
+GAIT_FOOT_FIELDS = ("contact", "touchdowns", "slip", "apex_sum", "prev", "apex")
+GAIT_FEET = ("left", "right")
+
+
+def gait_fields(nu: int) -> Dict[str, Tuple[int, int]]:
+    """(first column, width) of each field of the per-robot gait record (include/duck_fleet.h duck_fleet_gait;
+    DUCK_FLEET_GAIT_SIZE(nu) words in all): the seven per-actuator blocks, ``periods``, ``double_support``,
+    ``flight`` and, per foot, ``left_contact`` ... ``right_apex``."""
+    nu = int(nu)
+    at = lambda field, *f: HEADERS.value(f"DUCK_FLEET_GAIT_{field}({', '.join(str(int(v)) for v in (nu, *f))})")  # noqa: E731
+    out = {name: (at(name.upper()), nu) for name in GAIT_ACTUATOR_FIELDS}
+    out.update({name: (at(name.upper()), 1) for name in ("periods", "double_support", "flight")})
+    for f, foot in enumerate(GAIT_FEET):
+        for name in GAIT_FOOT_FIELDS:
+            out[f"{foot}_{name}"] = (at("FOOT", f) + HEADERS.consts[f"DUCK_FLEET_GAIT_FOOT_{name.upper()}"], 1)
+    assert max(o + w for o, w in out.values()) == HEADERS.value(f"DUCK_FLEET_GAIT_SIZE({nu})")
+    return out
+
+
+def gait_desc(m, force_frac: float = 0.9, speed_frac: float = 1.0):
+    """duck_fleet_gait_desc (include/duck_fleet_gait.h) of a compiled model: the feet's velocity and position sensors by
+    name, and the saturation thresholds -- ``force_frac`` of each force-limited actuator's largest |forcerange|
+    (+inf for one without a limit: never saturated), ``speed_frac`` of the reference loop's max_motor_velocity."""
+    from .native import FLEET_MAX_NU, DuckError, DuckFleetGaitDesc
+    if m.nu > FLEET_MAX_NU:
+        raise DuckError(f"the fleet kernels take at most {FLEET_MAX_NU} actuators, the model has {m.nu}")
+    if not (float(force_frac) >= 0 and float(speed_frac) >= 0):
+        raise DuckError(f"the gait thresholds are fractions >= 0, got {force_frac!r}, {speed_frac!r}")
+    d = DuckFleetGaitDesc()
+    names = m.names["sensor"]
+    for f, site in enumerate(constants.FEET_SITES):
+        d.foot_linvel[f] = int(m.sensor_adr[names.index(f"{site}_global_linvel")])
+        d.foot_pos[f] = int(m.sensor_adr[names.index(constants.FEET_POS_SENSOR[f])])
+    for a in range(FLEET_MAX_NU):
+        limited = a < m.nu and bool(m.actuator_forcelimited[a])
+        d.force_sat[a] = float(force_frac) * float(np.abs(m.actuator_forcerange[a]).max()) if limited else float("inf")
+    d.speed_sat = float(speed_frac) * MAX_MOTOR_VELOCITY
+    return d
+
+
 class FleetInfer:
     """The deployment loop of ``MjInfer`` for ``num_robots`` robots at once, resident on the device: one
     control period is four launches on one stream -- duck_physics_step (10 substeps, with the aux record),
@@ -310,6 +354,17 @@ class FleetInfer:
     that starts elsewhere is the caller's to load with ``load_state``).
     With no log set (``following()`` False) the loop enqueues exactly the launches above.
 
+    Gait and servo load (off by default; ``set_gait(on, force_frac, speed_frac)`` or ``gait=(on, force_frac,
+    speed_frac)``): one more launch after the actuation and before the recorder's, duck_fleet_gait: physics -> observe ->
+    [sense_delay or sensor_delay] -> [disturb] -> policy or follow -> actuate or actuate_delayed -> [gait] -> [record].
+    Per robot and while it is alive it sums, per actuator, the squared force, |force x joint speed| and the squared
+    action change, keeps the peak force and joint speed and counts the periods at the force and the speed limit; per
+    foot it counts contact periods and touchdowns and sums the slip speed squared and the swing clearance; and it
+    counts the periods of double support and of flight (``gait_records()``, ``gait_report``, ``gait_summary``). The
+    samples are the period's last substep's (50 Hz). It reads the loop and writes its own record only; with it off
+    (``gaited()`` False) the loop enqueues exactly the launches above. A ``replay()`` has it off: a frame does not
+    carry the gait state.
+
     Several policies (``onnx_model_path`` a list or tuple of K paths, at most DUCK_POLICY_MAX_POLICIES, all of one
     architecture and all with or all without a normaliser): the robots are policy-major, segment k --
     ``policy_robots[k]`` robots, by default ``num_robots / K`` each -- is served by file k, and duck_policy_act_multi
@@ -327,7 +382,7 @@ class FleetInfer:
     segments and identically distributed, not common random numbers."""
 
     # control periods per captured graph (200 launches; 50 more with disturbances, 50 more with an IMU or encoder delay, 50 more
-    # with a recorder: 400 at the most)
+    # with the gait record, 50 more with a recorder: 400 at the most)
     CHUNK = 50
 
     def __init__(self, model_path: str = "flat_terrain", onnx_model_path: Optional[str] = None, num_robots: int = 1,
@@ -335,7 +390,7 @@ class FleetInfer:
                  randomize: Optional[int] = None, command_schedule: Optional[tuple] = None,
                  pushes: Optional[tuple] = None, noise: Optional[tuple] = None, recorder: Optional[tuple] = None,
                  robot_offset: int = 0, latency: Optional[tuple] = None, follow: Optional[tuple] = None,
-                 policy_robots: Optional[Sequence[int]] = None):
+                 policy_robots: Optional[Sequence[int]] = None, gait: Optional[tuple] = None):
         import ctypes as C
 
         from .native import DuckError, check
@@ -436,6 +491,9 @@ class FleetInfer:
         # following a log (include/duck_fleet.h duck_fleet_follow): off
         self.log = self.log_id = self.log_tick = self.score = None
         self.log_base = 0
+        # gait and servo load (include/duck_fleet.h duck_fleet_gait): off
+        self.gait_fields = gait_fields(nu)
+        self.gait_desc = self.gait_rec = None
         # the flight recorder (include/duck_fleet.h duck_fleet_record): off
         self.frame_fields = frame_fields(int(m.nq), int(m.nv), nu)
         self.ring = self.rec_head = self.rec_after = None
@@ -455,13 +513,16 @@ class FleetInfer:
             self.set_latency(*latency)
         if follow is not None:
             self.set_log(*follow)
+        if gait is not None:
+            self.set_gait(*gait)
 
     def restart(self) -> None:
         """Every robot back to the loop's start, with the randomisation record ``dr`` as it is now.
         MJInferBase.__init__: MjData at qpos0 with zero ctrl, one mj_step, then the home keyframe's qpos and
         ctrl (the velocity of that first step is kept); mujoco_infer.py:49-60 for the control record. The
         period count goes back to 0, a command schedule to its segment 0, a recorder to no frames, a latency
-        to its first period (the delay line fills anew) and a followed log to its row 0 with zero scores."""
+        to its first period (the delay line fills anew), a followed log to its row 0 with zero scores and the gait
+        record to zero."""
         m, n = self.model, self.num_robots
         col = lambda a: torch.tensor(np.asarray(a, dtype=np.float32)[:, None], device=self.device)  # noqa: E731
         key = m.names["key"].index("home")
@@ -582,13 +643,23 @@ class FleetInfer:
         self._launch("duck_fleet_disturb", self.robot_offset, self.tick, self.sched, self.sched_id, self.push, self.qvel,
                      self.ctl, self.obs, lead=(C.byref(self.dis),))
 
+    def gaited(self) -> bool:
+        """Whether the gait record is kept (duck_fleet_gait after the actuation)."""
+        return self.gait_rec is not None
+
+    def gait(self):
+        """duck_fleet_gait on this period's aux, qvel, ctl and alive: the servo loads, the action rate, the feet."""
+        import ctypes as C
+        self._launch("duck_fleet_gait", self.qvel, self.aux, self.ctl, self.alive, self.gait_rec,
+                     lead=(C.byref(self.gait_desc),))
+
     def record(self):
         """duck_fleet_record: this period's frame into the ring of every robot not yet frozen."""
         self._launch("duck_fleet_record", self.rec_depth, self.rec_post, self.qpos, self.qvel, self.warm, self.aux,
                      self.ctl, self.obs, self.action, self.alive, self.rec_head, self.rec_after, self.ring)
 
     def _periods(self, k: int, rec: Optional[torch.Tensor] = None, t0: int = 0):
-        disturbed, recording = self.disturbed(), self.ring is not None
+        disturbed, recording, gaited = self.disturbed(), self.ring is not None, self.gaited()
         sense = self.latent() and self.lat_sense
         encoder = self.latent() and self.lat_encoder      # the IMU and the encoders in one launch, in sense_delay's place
         for t in range(k):
@@ -603,6 +674,8 @@ class FleetInfer:
             if rec is not None:
                 rec[t0 + t].copy_(self.obs)
             self.act()
+            if gaited:
+                self.gait()
             if recording:
                 self.record()
 
@@ -895,6 +968,30 @@ class FleetInfer:
         """A log from ``path`` (``load_log``, the module's function), for ``set_log``."""
         return load_log(path)
 
+    # --- gait and servo load (include/duck_fleet.h duck_fleet_gait) ---------------------------------------
+    def set_gait(self, on: bool = True, force_frac: float = 0.9, speed_frac: float = 1.0) -> None:
+        """Keep the gait record: from now on a period enqueues duck_fleet_gait after the actuation. A period counts
+        as force-saturated for an actuator at ``force_frac`` of its force limit and above, as speed-saturated at
+        ``speed_frac`` of the reference loop's max_motor_velocity (5.24 rad/s) and above (``gait_desc``). A new
+        record of zeros, [N][DUCK_FLEET_GAIT_SIZE(nu)] float32 on the device; it equals ``acc`` in its periods
+        when set right after ``restart()`` or ``reset_report()``, which zero both. ``on=False`` turns it off.
+        Switching it drops the captured graph."""
+        self.graph = None
+        if not on:
+            self.gait_desc = self.gait_rec = None
+            return
+        self.gait_desc = gait_desc(self.model, force_frac, speed_frac)
+        width = HEADERS.value(f"DUCK_FLEET_GAIT_SIZE({self.num_dofs})")
+        self.gait_rec = torch.zeros(self.num_robots, width, dtype=torch.float32, device=self.device)
+
+    def gait_records(self) -> np.ndarray:
+        """The raw gait record [N][DUCK_FLEET_GAIT_SIZE(nu)] float32 (``gait_fields``; ``gait_report`` reads it)."""
+        from .native import DuckError
+        if self.gait_rec is None:
+            raise DuckError("no gait record is kept (set_gait)")
+        torch.cuda.synchronize(self.device)
+        return self.gait_rec.cpu().numpy()
+
     # --- the flight recorder (include/duck_fleet.h duck_fleet_record) ----------------------------------
     def set_recorder(self, depth: Optional[int], post: int = 0) -> None:
         """Keep every robot's last ``depth`` control periods on the device, frozen ``post`` periods after the
@@ -944,7 +1041,7 @@ class FleetInfer:
         the one before it, with an encoder delay the encoder line from their ``qpos`` and ``qvel``; a robot whose
         IMU or encoder delay reaches 2 cannot be replayed from the oldest frame it holds.
         Of a following fleet the replay carries the robot's log and ``log_tick`` at the frame's period (its scores
-        start at zero).
+        start at zero). The replay keeps no gait record (``gaited()`` False): a frame does not carry the gait state.
         The loop is a pure function of what a frame holds, that record and that stream, so running the replay
         k periods reproduces the k periods the robot ran after that frame, bit for bit. The fleet's settings
         are taken as they are now: they must not have changed since the frame was written."""
@@ -1048,6 +1145,8 @@ class FleetInfer:
     def reset_report(self) -> None:
         self.acc.zero_()
         self.alive.fill_(1.0)
+        if self.gait_rec is not None:
+            self.gait_rec.zero_()
 
     def report(self) -> Dict[str, np.ndarray]:
         """Per robot: periods survived, fell, mean vx / vy / wz while alive, rms linear and yaw tracking
@@ -1092,6 +1191,85 @@ def grid_report(rep: Dict[str, np.ndarray], acc: np.ndarray, cells: np.ndarray, 
                     "mean_vx": stat(tot[1]), "mean_vy": stat(tot[2]), "mean_wz": stat(tot[3]),
                     "rms_lin_err": None if stat(tot[4]) is None else float(np.sqrt(stat(tot[4]))),
                     "rms_yaw_err": None if stat(tot[5]) is None else float(np.sqrt(stat(tot[5])))})
+    return out
+
+
+def _gait_nu(width: int) -> int:
+    """nu of a gait record ``width`` = DUCK_FLEET_GAIT_SIZE(nu) words wide."""
+    from .native import FLEET_MAX_NU, DuckError
+    for nu in range(1, FLEET_MAX_NU + 1):
+        if HEADERS.value(f"DUCK_FLEET_GAIT_SIZE({nu})") == int(width):
+            return nu
+    raise DuckError(f"{width} words are no gait record (DUCK_FLEET_GAIT_SIZE(nu), nu <= {FLEET_MAX_NU})")
+
+
+def _gait_stats(g: np.ndarray, distance: np.ndarray, weight: float, dt: float) -> Dict[str, np.ndarray]:
+    """The statistics of gait records ``g`` [R][G] float64 whose robots covered ``distance`` [R] metres and weigh
+    ``weight`` newtons: what ``gait_report`` returns. A zero denominator gives NaN."""
+    F = gait_fields(_gait_nu(g.shape[1]))
+    col = lambda name: g[:, F[name][0]:F[name][0] + F[name][1]]  # noqa: E731
+    feet = lambda name: np.concatenate([col(f"{foot}_{name}") for foot in GAIT_FEET], 1)  # noqa: E731
+
+    def over(a, b):
+        a, b = np.broadcast_arrays(np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64))
+        out = np.full(a.shape, np.nan)
+        np.divide(a, b, out=out, where=b != 0)
+        return out
+    per = col("periods")
+    some = per > 0
+    contact, touchdowns = feet("contact"), feet("touchdowns")
+    with np.errstate(invalid="ignore"):
+        return {"periods": per[:, 0],
+                "force_rms": np.sqrt(over(col("force_sq"), per)), "force_peak": np.where(some, col("force_max"), np.nan),
+                "force_sat": over(col("force_sat"), per), "speed_peak": np.where(some, col("speed_max"), np.nan),
+                "speed_sat": over(col("speed_sat"), per), "mean_power": over(col("work"), per),
+                "action_rate_rms": np.sqrt(over(col("action_rate"), per)),
+                "duty_factor": over(contact, per), "step_frequency": over(touchdowns, per * dt),
+                "slip_rms": np.sqrt(over(feet("slip"), contact)), "clearance": over(feet("apex_sum"), touchdowns),
+                "double_support": over(col("double_support"), per)[:, 0], "flight": over(col("flight"), per)[:, 0],
+                "cost_of_transport": over(col("work").sum(1) * dt, weight * np.asarray(distance, dtype=np.float64))}
+
+
+def _gait_weight(model) -> float:
+    """M g of the nominal model, in newtons: its bodies' total mass times the norm of its gravity."""
+    return float(np.sum(np.asarray(model.body_mass, dtype=np.float64)) *
+                 np.linalg.norm(np.asarray(model.opt_gravity, dtype=np.float64)))
+
+
+def gait_report(gait, acc, model, dt: float = 0.02) -> Dict[str, np.ndarray]:
+    """Per robot, in float64, from the gait record ``gait`` [N][G] (``FleetInfer.gait_records()``), ``acc`` [N][6]
+    and the compiled ``model`` (its total mass and gravity; the nominal one, whatever a robot's randomisation):
+    per actuator [N][nu] ``force_rms`` and ``force_peak`` (the actuator's force unit, N m for the duck's joints),
+    ``force_sat`` and ``speed_sat`` (the share of the periods at the limit), ``speed_peak`` (rad/s), ``mean_power``
+    (mean |force x joint speed|, W) and ``action_rate_rms``; per foot [N][2] (left, right) ``duty_factor``,
+    ``step_frequency`` (Hz: touchdowns / (periods dt)), ``slip_rms`` (m/s, over the contact periods) and
+    ``clearance`` (m: the mean over the touchdowns of the swing's highest sample over the landing sample); per
+    robot [N] ``periods``, ``double_support`` and ``flight`` (shares of the periods) and ``cost_of_transport`` =
+    sum of work dt / (M g |(mean_vx, mean_vy)| periods dt). All of 50 Hz samples. A zero denominator gives NaN."""
+    g, a = np.asarray(gait, dtype=np.float64), np.asarray(acc, dtype=np.float64)
+    return _gait_stats(g, np.hypot(a[:, 1], a[:, 2]) * dt, _gait_weight(model), dt)
+
+
+def gait_summary(gait, acc, rows, model, dt: float = 0.02) -> dict:
+    """``gait_report`` of the robots ``rows`` (indices or a mask; None: all) pooled into one: sums of the sums, maxima
+    of the maxima, the distance the sum of the robots' distances. A plain dict for a JSON report: ``"count"``,
+    ``"actuators"`` (their names), ``"feet"``, and every statistic as a float or a list, None where ``gait_report``
+    gives NaN."""
+    g, a = np.asarray(gait, dtype=np.float64), np.asarray(acc, dtype=np.float64)
+    if rows is not None:
+        g, a = g[rows], a[rows]
+    F = gait_fields(_gait_nu(g.shape[1]))
+    pooled = g.sum(0, keepdims=True)
+    for name in ("force_max", "speed_max"):
+        o, w = F[name]
+        pooled[0, o:o + w] = g[:, o:o + w].max(0) if len(g) else 0.0
+    for foot in GAIT_FEET:      # the state words mean nothing once pooled
+        pooled[0, F[f"{foot}_prev"][0]] = pooled[0, F[f"{foot}_apex"][0]] = 0.0
+    stats = _gait_stats(pooled, [np.hypot(a[:, 1], a[:, 2]).sum() * dt], _gait_weight(model), dt)
+    num = lambda v: None if np.isnan(v) else float(v)  # noqa: E731
+    out = {"count": int(len(g)), "actuators": list(model.names["actuator"]), "feet": list(GAIT_FEET)}
+    for key, v in stats.items():
+        out[key] = num(v[0]) if np.ndim(v[0]) == 0 else [num(x) for x in v[0]]
     return out
 
 
@@ -1762,6 +1940,41 @@ def policies_doc(paths, rep: Dict[str, np.ndarray], acc: np.ndarray, seg, n_peri
             "paired_wins": paired_wins(rep["periods"], len(rows)).tolist()}
 
 
+def add_gait_arguments(p) -> None:
+    p.add_argument("--gait", action="store_true", default=False,
+                   help="keep the gait and servo-load record and report it: for the fleet, per command cell and per policy")
+    p.add_argument("--gait_force_frac", type=float, default=0.9, metavar="F",
+                   help="a period counts as force-saturated at this fraction of the actuator's force limit")
+    p.add_argument("--gait_speed_frac", type=float, default=1.0, metavar="F",
+                   help="a period counts as speed-saturated at this fraction of the motors' 5.24 rad/s")
+
+
+def gait_plan(args) -> Optional[tuple]:
+    """``FleetInfer``'s ``gait`` keyword from the command line's arguments: None without ``--gait``."""
+    if not args.gait:
+        return None
+    if not (args.gait_force_frac >= 0 and args.gait_speed_frac >= 0):
+        raise ValueError("--gait_force_frac and --gait_speed_frac want fractions >= 0")
+    return (True, float(args.gait_force_frac), float(args.gait_speed_frac))
+
+
+def add_gait_report(doc: dict, gait, acc, model, cell, seg=None, dt: float = 0.02) -> dict:
+    """What ``--gait`` adds to the command line's report ``doc``, in place: ``"gait"``, ``gait_summary`` of the
+    whole fleet; ``"gait"`` in every row of ``doc["cells"]``, the summary of the cell's robots (``cell`` [N], each
+    robot's command cell); and, with ``seg`` [K + 1] (several policies), ``"gait"`` in every row of
+    ``doc["policies"]``. ``gait=None`` (no record was kept) adds nothing."""
+    if gait is None:
+        return doc
+    cell = np.asarray(cell)
+    doc["gait"] = gait_summary(gait, acc, None, model, dt)
+    for c, row in enumerate(doc.get("cells", ())):
+        row["gait"] = gait_summary(gait, acc, cell == c, model, dt)
+    if seg is not None:
+        for k, row in enumerate(doc.get("policies", ())):
+            row["gait"] = gait_summary(gait, acc, slice(int(seg[k]), int(seg[k + 1])), model, dt)
+    return doc
+
+
 def build_parser():
     import argparse
     p = argparse.ArgumentParser(description="Run an exported policy in the deployment loop for a fleet of robots")
@@ -1780,6 +1993,7 @@ def build_parser():
     add_latency_arguments(p)
     add_recorder_arguments(p)
     add_follow_arguments(p)
+    add_gait_arguments(p)
     p.add_argument("--policies", type=str, nargs="+", default=None, metavar="P",
                    help="several exported policies in one fleet, --num_robots / K robots each on the same models, "
                         "commands, pushes and delays; the report ranks them")
@@ -1801,6 +2015,7 @@ def parse_arguments(argv=None):
         p.error("-o/--onnx_model_path is required (unless --follow LOG or --policies P1 P2 ... is given)")
     try:
         follow_plan(args)
+        gait_plan(args)
     except ValueError as e:
         p.error(str(e))
     if args.record_falls is None and args.record_out is not None:
@@ -1830,7 +2045,7 @@ def main(argv=None) -> int:
     fleet = FleetInfer(args.model_path, args.onnx_model_path if args.policies is None else list(args.policies),
                        args.num_robots, reference_data=args.reference_data,
                        standing=args.standing, device=args.device, randomize=args.randomize,
-                       follow=None if log is None else (log, None))
+                       follow=None if log is None else (log, None), gait=gait_plan(args))
     if log is None:            # (a followed log brings its own commands)
         fleet.set_commands(over(cells[np.arange(one.num_robots) % len(cells)]))
     if plan is not None:
@@ -1904,6 +2119,9 @@ def main(argv=None) -> int:
                                 None if plan is None or plan["pushes"] is None else
                                 (plan["push_cell"], args.push_at, args.push_every, args.recovery_window),
                                 None if delays is None else (delays["cell"], delays["cells"], args.delay_jitter)))
+    if gait_plan(args) is not None:
+        add_gait_report(doc, fleet.gait_records(), fleet.acc.cpu().numpy(), fleet.model,
+                        over(np.arange(one.num_robots) % len(cells)), fleet.policy_seg if args.policies is not None else None)
     if follow_doc is not None:
         doc["follow"] = follow_doc
         if following["fit_out"]:
